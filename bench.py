@@ -8,6 +8,10 @@ the length-bucketed fp64 block Gauss-Seidel E-step run to per-document convergen
 replay), deterministic sufficient statistics, the class_word reduction over RCCL when N > 1, the
 M-step and the alpha Newton (csrc/hip/lda_gs64.hip; lda-c's double arithmetic).
 
+A plain run measures the headline alone: it builds the corpus, warms up, times the K steps, trains
+once to convergence (``value``), writes the outputs if asked (--dump-outputs) and prints the result
+line.  ``--full`` adds the legs marked [--full] below.
+
 What is measured, at every N (one process per GPU, `torchrun --nproc-per-node N`):
 
 * ``value`` -- LDA docs/s TO CONVERGENCE on the BASELINE config: ONE 1-day corpus (1M events, seed
@@ -18,18 +22,18 @@ What is measured, at every N (one process per GPU, `torchrun --nproc-per-node N`
   docs x EM iterations / wall time, the clock includes the engine's construction.
 * ``ms_per_step`` -- W untimed warm-up EM iterations, then exactly K EM iterations bracketed by
   barrier + synchronize, max over ranks (``window_docs_per_sec``).
-* ``weak_docs_per_sec`` -- secondary: rank r featurizes its own day (seed 1000 r), the ranks agree on
+* ``weak_docs_per_sec`` -- [--full] secondary: rank r featurizes its own day (seed 1000 r), the ranks agree on
   the union vocabulary and train the N-day corpus to convergence, one day per GPU (at N = 1 the same
   run as ``value``).
-* ``e2e_wall_s`` -- the whole ml_ops flow pipeline (load, flow_pre, lda_pre, lda, lda_post,
+* ``e2e_wall_s`` -- [--full] the whole ml_ops flow pipeline (load, flow_pre, lda_pre, lda, lda_post,
   flow_post) on a fresh synthetic day, in this process (warm: interpreter, torch, HIP and the
   kernels already loaded); row-sharded over the N ranks at N > 1 (pipeline/sharded.py).
-* ``e2e_cold_wall_s`` -- the same run as fresh child processes (`python -m oni_ml_amd ml_ops
+* ``e2e_cold_wall_s`` -- [--full] the same run as fresh child processes (`python -m oni_ml_amd ml_ops
   20160122 flow TOL ...`, one per rank, their own process group), timed from spawn to exit:
   interpreter start-up, imports, HIP init, code-object loads and the pipeline -- what the
   reference's `time` prefixes measure (ml_ops.sh:57,67,80,84,108).  This is the ml_ops wall-clock.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
   (N > 1: python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...)
   CPU rehearsal of the multi-rank path: --device cpu (gloo, torch backend).
 """
@@ -131,6 +135,39 @@ def _to_convergence(args, corpus, ctx, dev, seed, local):
                doc_range=list(eng.doc_range), docs_this_rank=eng.D, nnz_this_rank=eng.corpus.nnz)
     del eng
     return v, rec
+
+
+DUMP_BYTES = 64 * 1000 * 1000     # all files of --dump-outputs together
+DUMP_SEED = 20160122              # of the sample an array too large for its share is cut to
+
+
+def _dump_outputs(path, eng, recs, rank):
+    """What the timed path left its caller after the last timed step, as <path>/<name>.npy (float64; rank 0
+    writes): ``history`` [steps, 3], the (likelihood, alpha, alpha_ss) that em_iterations_pipelined returned
+    for every timed iteration (its convergence column follows from the likelihoods and is infinite at the
+    window's first iteration: left out); ``gamma`` [docs, K], the variational document-topic parameters of all
+    ranks' documents; ``log_beta`` [K, V], the model as lda-c saves it.  An array above its share of
+    DUMP_BYTES is cut along its longer axis to a fixed, seeded sample (the same rows or columns every run;
+    ``sampled`` in the returned record names it), the history to its last iterations."""
+    hist = np.asarray([(r[0], r[2], r[4]) for r in recs], np.float64).reshape(len(recs), 3)
+    arrays = dict(history=hist[-(DUMP_BYTES // 8 // 24):], gamma=eng.gather_gamma(),
+                  log_beta=eng.log_beta())                                # collectives: every rank calls
+    if rank != 0:
+        return {}
+    os.makedirs(path, exist_ok=True)
+    share = (DUMP_BYTES - arrays["history"].nbytes - 4096) // 2          # 4096: the three .npy headers
+    shapes, sampled = {}, {}
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        if name != "history" and a.nbytes > share:
+            ax = int(np.argmax(a.shape))
+            n = max(1, share // (a.nbytes // a.shape[ax]))
+            keep = np.sort(np.random.default_rng(DUMP_SEED).choice(a.shape[ax], size=n, replace=False))
+            sampled[name] = dict(axis=ax, of=a.shape[ax], seed=DUMP_SEED)
+            a = np.ascontiguousarray(np.take(a, keep, axis=ax))
+        np.save(os.path.join(path, name + ".npy"), a)
+        shapes[name] = list(a.shape)
+    return dict(dump_outputs=dict(dir=path, arrays=shapes, sampled=sampled))
 
 
 def _shared_tmpdir(ctx, prefix):
@@ -258,10 +295,16 @@ def main():
     ap.add_argument("--streams", type=int, default=4, help="HIP streams for the E-step buckets")
     ap.add_argument("--batch", type=int, default=5,
                     help="EM iterations per host read-back in the timed window (LDAEngine.run() batches 8)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the secondary legs: the weak-scaling run (N > 1) and the ml_ops wall-clock, warm "
+                         "and cold (--weak, --e2e, --e2e-cold choose among them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one left a caller (gamma, log_beta, the "
+                         "timed steps' likelihood / alpha history) as DIR/<name>.npy, float64, 64 MB at the most")
     ap.add_argument("--converge", type=int, default=1, help="time a full random-init run to convergence (value)")
-    ap.add_argument("--weak", type=int, default=1, help="N > 1: also the one-day-per-GPU weak-scaling run")
-    ap.add_argument("--e2e", type=int, default=1, help="time the whole ml_ops flow pipeline in-process (warm)")
-    ap.add_argument("--e2e-cold", type=int, default=1, help="time ml_ops as fresh child processes (cold)")
+    ap.add_argument("--weak", type=int, default=1, help="--full, N > 1: also the one-day-per-GPU weak-scaling run")
+    ap.add_argument("--e2e", type=int, default=1, help="--full: time the whole ml_ops flow pipeline in-process (warm)")
+    ap.add_argument("--e2e-cold", type=int, default=1, help="--full: time ml_ops as fresh child processes (cold)")
     ap.add_argument("--e2e-timeout", type=float, default=900.0)
     ap.add_argument("--device", default="cuda", choices=["cuda", "cpu"], help="cpu: gloo/torch rehearsal")
     ap.add_argument("--scaling", default="strong", choices=["weak", "strong"],
@@ -270,6 +313,10 @@ def main():
     ap.add_argument("--e2e-tol", type=float, default=1e-5,
                     help="suspicion threshold of the timed ml_ops runs (1e-5 flags ~5 %% of the synthetic day)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if not args.full:
+        args.weak = args.e2e = args.e2e_cold = 0
     if args.topics != 20 and (args.e2e or args.e2e_cold):
         # the ml_ops legs time the reference's strict pipeline, whose lda_post is hard-wired to 20 topics
         _log(f"K = {args.topics}: no ml_ops legs (strict lda_post is K = 20 only)")
@@ -300,13 +347,14 @@ def main():
         batches = [min(args.batch, n - b) for b in range(0, n, args.batch)]
         recs = eng.em_iterations_pipelined(batches, True, docs_global, stop=False)
         assert len(recs) == n, (len(recs), n)
+        return recs
 
     _log("timed window")
     run_iters(args.warmup)
     ctx.barrier()
     _sync(dev)
     t1 = time.perf_counter()
-    run_iters(args.steps)
+    timed_recs = run_iters(args.steps)
     _sync(dev)
     ctx.barrier()
     dt = ctx.allreduce_max(time.perf_counter() - t1)
@@ -314,6 +362,9 @@ def main():
     window_value = docs_global * args.steps / dt
     it = eng.iters.cpu().numpy()
     extra = dict(var_iter_mean=round(float(it.mean()), 3), var_iter_max=int(it.max()), var_max_iter=eng.var_max_iter)
+    if args.dump_outputs:
+        _log(f"writing the outputs to {args.dump_outputs}")
+        extra.update(_dump_outputs(args.dump_outputs, eng, timed_recs, rank))
     lens = eng.corpus.lengths()
     by_len = {}
     for lo, hi in ((0, 16), (16, 64), (64, 256), (256, 1024), (1024, 4096), (4096, 1 << 40)):

@@ -1,6 +1,6 @@
 #!/bin/bash
 # BASELINE.json configs on one MI355X (per-GPU shard of the 8-GPU configs):
-#   headline  flow 1-day, K=20
+#   headline  flow 1-day, K=20          (bench.py --full: with the ml_ops wall-clock legs)
 #   config 3  flow 1-day, K=50          (8 GPUs: one day per GPU, weak scaling)
 #   config 4  DNS 1-day (2M queries), K=20
 #   config 5  flow 30-day / 8 = 12.5M events per GPU, K=100
@@ -22,7 +22,7 @@ print(f"{sys.argv[2]:10s} K={c['model'][-3:]} docs={c.get('docs', c.get('docs_pe
       f"converge={d.get('converge_seconds')}s/{d.get('converge_em_iters')}it corpus_build={d.get('corpus_build_s')}s")
 PY
 }
-run headline "$@" && \
+run headline --full "$@" && \
 run flow_k50 --topics 50 --e2e 0 --e2e-cold 0 "$@" && \
 run dns_k20 --corpus dns --e2e 0 --e2e-cold 0 "$@" && \
 run flow30d_k100 --topics 100 --events 12500000 --e2e 0 --e2e-cold 0 "$@"

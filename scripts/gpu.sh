@@ -6,7 +6,7 @@
 # steps:
 #   tests     pytest -m gpu (PYTEST_FILES, default tests/; PYTEST_K: -k filter)
 #   smoke     __graft_entry__.smoke()
-#   bench     python bench.py $BENCH_ARGS                       -> $OUT/bench.json
+#   bench     python bench.py $BENCH_ARGS (default --full)      -> $OUT/bench.json
 #   prof      rocprofv3 --kernel-trace --stats of a short bench -> $OUT/prof_summary.md, timeline.txt
 #   phases    scripts/bench_gs64.py --phases $PHASES_ARGS (per-bucket E-step times, phase cycles per chunk)
 #   configs   scripts/bench_configs.sh (every BASELINE config on one GPU)
@@ -43,7 +43,7 @@ for s in "$@"; do
       timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke.log" 2>&1 || stop smoke $?
       tail -3 "$OUT/smoke.log" ;;
     bench)
-      timeout -k 10 600 python -u bench.py ${BENCH_ARGS:-} > "$OUT/bench.log" 2>&1 || { tail -20 "$OUT/bench.log"; stop bench 1; }
+      timeout -k 10 600 python -u bench.py ${BENCH_ARGS:---full} > "$OUT/bench.log" 2>&1 || { tail -20 "$OUT/bench.log"; stop bench 1; }
       grep '^{' "$OUT/bench.log" | tail -1 > "$OUT/bench.json"; cut -c1-1500 "$OUT/bench.json" ;;
     prof)
       rm -rf "$OUT/prof"; mkdir -p "$OUT/prof"

@@ -110,7 +110,7 @@ def test_two_rank_em_matches_single_rank(tmp_path, exchange):
 
 
 def test_bench_two_rank_cpu_rehearsal():
-    """bench.py at N = 2 on gloo: every field of the BENCH line -- the strong-scaling 1-day value (one
+    """bench.py --full at N = 2 on gloo: every field of the BENCH line -- the strong-scaling 1-day value (one
     corpus sharded over the ranks), the weak-scaling secondary, the row-sharded ml_ops pipeline in-process
     (warm) and as fresh child processes (cold)."""
     import json
@@ -119,7 +119,7 @@ def test_bench_two_rank_cpu_rehearsal():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                         "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), "bench.py", "--gpus", "2",
-                        "--steps", "1", "--warmup", "1", "--events", "5000", "--device", "cpu"],
+                        "--steps", "1", "--warmup", "1", "--events", "5000", "--device", "cpu", "--full"],
                        cwd=root, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])

@@ -110,7 +110,7 @@ def test_bench_strong_scaling_cpu_rehearsal(world):
 
 
 def test_bench_world8_gloo_shards_chain_and_weak_vocabulary():
-    """bench.py at N = 8 over gloo (the RCCL code paths rehearsed on the CPU; no hardware claim):
+    """bench.py --full at N = 8 over gloo (the RCCL code paths rehearsed on the CPU; no hardware claim):
     the strong-scaling shards tile the one-day corpus and are the engine's chain-aware cut
     (dist.engine_bounds: the longest document's rank carries no more than the cut's modelled share), and
     the weak run's union vocabulary (one day per rank, seeds 1000 r) equals a one-process union of the
@@ -122,7 +122,7 @@ def test_bench_world8_gloo_shards_chain_and_weak_vocabulary():
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world),
                         "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), "bench.py", "--gpus",
                         str(world), "--steps", "1", "--warmup", "1", "--events", str(events), "--device", "cpu",
-                        "--e2e", "0", "--e2e-cold", "0"],
+                        "--full", "--e2e", "0", "--e2e-cold", "0"],
                        cwd=ROOT, capture_output=True, text=True, timeout=1200,
                        env=dict(os.environ, OMP_NUM_THREADS="1"))
     assert r.returncode == 0, r.stderr[-3000:]

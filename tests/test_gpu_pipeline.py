@@ -86,14 +86,21 @@ def test_hip_estimate_resume_exact(tmp_path):
     assert np.array_equal(res.gamma, full.gamma)
 
 
-def test_bench_smoke():
+def test_bench_smoke(tmp_path):
     r = subprocess.run([sys.executable, "bench.py", "--steps", "3", "--warmup", "1", "--events", "200000",
-                        "--converge", "0", "--e2e", "0", "--e2e-cold", "0"], cwd=ROOT, capture_output=True, text=True,
-                       timeout=600)
+                        "--converge", "0", "--e2e", "0", "--e2e-cold", "0", "--dump-outputs", str(tmp_path / "out")],
+                       cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]
     out = json.loads(line)
-    assert out["n_gpus"] == 1 and out["value"] > 0 and out["steps"] == 3
+    assert out["n_gpus"] == 1 and out["value"] > 0 and out["steps"] == 3 and out["ms_per_step"] > 0
+    # --dump-outputs: what the last timed step left -- gamma of every document, the model, the steps' history
+    D, V = out["config"]["docs"], out["config"]["vocab"]
+    got = {n: np.load(tmp_path / "out" / f"{n}.npy") for n in ("history", "gamma", "log_beta")}
+    assert [got[n].shape for n in ("history", "gamma", "log_beta")] == [(3, 3), (D, 20), (20, V)]
+    assert all(a.dtype == np.float64 and np.isfinite(a).all() for a in got.values())
+    assert (got["history"][:, 0] < 0).all() and (got["gamma"] > 0).all() and (got["log_beta"] <= 0).all()
+    assert sum(a.nbytes for a in got.values()) <= 64e6
 
 
 def test_lda_inf_hip_matches_references():

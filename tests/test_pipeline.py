@@ -377,3 +377,24 @@ def test_flow_post_paths_byte_identical(tmp_path, monkeypatch, compat):
     cfg.resume = True
     run(cfg, device="cpu", log=lambda *a, **k: None)
     assert (d / "ml" / "flow_results.csv").read_bytes() == outs["plain"]["flow_results.csv"]
+
+
+def test_bench_plain_run_and_dump_outputs(tmp_path):
+    """bench.py on the CPU rehearsal path: a plain run reports the headline alone (no ml_ops legs: those are
+    --full's), --steps sets the timed steps, and --dump-outputs writes the last timed step's arrays, the
+    same from run to run."""
+    got = []
+    for d in ("a", "b"):
+        r = subprocess.run([sys.executable, "bench.py", "--device", "cpu", "--events", "3000", "--steps", "2",
+                            "--warmup", "1", "--dump-outputs", str(tmp_path / d)], cwd=ROOT, capture_output=True,
+                           text=True, timeout=600, env=dict(os.environ, OMP_NUM_THREADS="2"))
+        assert r.returncode == 0, r.stderr[-3000:]
+        out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+        assert out["steps"] == 2 and out["ms_per_step"] > 0 and out["value"] > 0 and out["converge_em_iters"] > 0
+        assert not [k for k in out if k.startswith("e2e_")]
+        got.append({n: np.load(tmp_path / d / f"{n}.npy") for n in ("history", "gamma", "log_beta")})
+        D, V = out["config"]["docs"], out["config"]["vocab"]
+        assert [got[-1][n].shape for n in ("history", "gamma", "log_beta")] == [(2, 3), (D, 20), (20, V)]
+        assert sorted(os.listdir(tmp_path / d)) == ["gamma.npy", "history.npy", "log_beta.npy"]
+    for n, a in got[0].items():
+        assert a.dtype == np.float64 and np.isfinite(a).all() and np.array_equal(a, got[1][n]), n

@@ -11,7 +11,11 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_pycache_prefix_only_when_site_packages_read_only(monkeypatch, tmp_path):
+    # the switches enable() honours come from the test, not from how this interpreter was started
+    # (python -B / PYTHONDONTWRITEBYTECODE, PYTHONPYCACHEPREFIX, ONI_PYCACHE)
     monkeypatch.setattr(sys, "pycache_prefix", None)
+    monkeypatch.setattr(sys, "dont_write_bytecode", False)
+    monkeypatch.delenv("ONI_PYCACHE", raising=False)
     monkeypatch.setenv("XDG_CACHE_HOME", str(tmp_path))
     torch_dir = os.path.dirname(importlib.util.find_spec("torch").origin)
     real = os.access
@@ -28,6 +32,10 @@ def test_pycache_prefix_only_when_site_packages_read_only(monkeypatch, tmp_path)
     monkeypatch.setattr(sys, "pycache_prefix", None)
     monkeypatch.setenv("ONI_PYCACHE", "0")
     assert pycache.enable() is None
+    # an interpreter that writes no bytecode gets no prefix either
+    monkeypatch.delenv("ONI_PYCACHE")
+    monkeypatch.setattr(sys, "dont_write_bytecode", True)
+    assert pycache.enable() is None and sys.pycache_prefix is None
 
 
 def test_fast_exit_keeps_outputs(tmp_path):
