@@ -152,6 +152,19 @@ PYBIND11_MODULE(_onihip, m) {
     oni::launch_score_events(a, S(stream));
   });
 
+  m.def("select_tile", []() { return oni::kSelectTile; });
+  m.def("select_work_words", [](int64_t n) { return oni::select_work_words(n); });
+  m.def("select_result_word", []() { return oni::select_result_word(); });
+  m.def("select_lowest", [](u key, u flag, int64_t n, int64_t limit, u work, u out, int64_t out_cap, int max_blocks,
+                            u stream) {
+    if (n <= 0 || n >= ((int64_t)1 << 31)) throw std::runtime_error("select_lowest: n outside 1 .. 2^31 - 1");
+    if (limit < 1 || limit > n || out_cap < limit) throw std::runtime_error("select_lowest: limit outside 1 .. n");
+    oni::SelectArgs a{P<const double>(key), P<const uint8_t>(flag), n, (unsigned)limit,
+                      (unsigned)((n + oni::kSelectTile - 1) / oni::kSelectTile), P<unsigned>(work),
+                      P<long long>(out), (unsigned)out_cap};
+    oni::launch_select_lowest(a, max_blocks, S(stream));
+  });
+
   m.def("flow_words", [](u hour, u minute, u second, u port_a, u port_b, u ipkt, u ibyt, u time_cuts,
                          int n_time, u ibyt_cuts, int n_ibyt, u ipkt_cuts, int n_ipkt, int64_t n, u time_out,
                          u time_bin, u ibyt_bin, u ipkt_bin, u word_port, u p_case, u src_prefix,

@@ -225,6 +225,28 @@ struct ScoreArgs {
 };
 void launch_score_events(const ScoreArgs& a, hipStream_t s);
 
+// MAXRESULTS (select_lowest.hip): the rows that a stable ascending sort of the flagged keys puts first.
+constexpr int kSelectTile = 2048;      // rows of one tile (256 threads x 8 rows); tiles are fixed and contiguous
+constexpr int kSelectPasses = 6;       // radix digits of 11, 11, 11, 11, 11 and 9 bits, most significant first
+constexpr int kSelectBins = 2048;      // histogram words per pass
+constexpr int kSelectStateWords = 8;   // 32-bit words of a pass's state {prefix lo, hi, need, all, flagged, m, -, -}
+struct SelectArgs {
+  const double* key;      // [n]
+  const uint8_t* flag;    // [n] non-zero: the row takes part
+  int64_t n;              // 0 < n < 2^31
+  unsigned limit;         // rows to select, >= 1
+  unsigned ntiles;        // ceil(n / kSelectTile)
+  unsigned* work;         // [select_work_words(n)]: kSelectPasses histograms, as many states, 2 counters per tile
+  long long* out;         // [out_cap] the selected rows, ascending by row
+  unsigned out_cap;       // >= min(limit, n)
+};
+size_t select_work_words(int64_t n);
+// word of `work` that holds, once the launches are done, the number of flagged rows; the next word holds
+// the number of selected rows m = min(limit, flagged)
+int select_result_word();
+// max_blocks: cap on the workgroups per launch (0: 2048); more tiles than that are grid-strided
+void launch_select_lowest(const SelectArgs& a, int max_blocks, hipStream_t s);
+
 // ------------------------------------------------------------ flow words ---
 struct FlowWordArgs {
   const double* hour;      // [n] col 4

@@ -1,6 +1,8 @@
 """Command line: ``python -m oni_ml_amd <command> ...`` (and scripts/ml_ops.sh).
 
-  ml_ops YYYYMMDD {flow|dns} [TOL] [options]   end-to-end run (reference ml_ops.sh:1-123)
+  ml_ops YYYYMMDD {flow|dns} [TOL] [MAXRESULTS] [options]
+                                               end-to-end run (reference ml_ops.sh:1-123); MAXRESULTS: only the
+                                               N lowest scores under TOL are written (-1: no limit)
   lda est <alpha> <k> <settings> <nproc> <corpus> <random|seeded|prefix> <dir>
                                                oni-lda-c command line (ml_ops.sh:80) on the MI355X engine
   lda inf <settings> <model-prefix> <corpus> <name>
@@ -57,7 +59,7 @@ def startup_marks() -> dict:
 
 SYNTAX = """ml_ops.sh syntax error
 Please run ml_ops.sh again with the correct syntax:
-./ml_ops.sh YYYYMMDD TYPE [TOL]
+./ml_ops.sh YYYYMMDD TYPE [TOL] [MAXRESULTS]
 for example:
 ./ml_ops.sh 20160122 dns 1e-6
 ./ml_ops.sh 20160122 flow"""
@@ -102,6 +104,9 @@ def cmd_ml_ops(argv):
     ap.add_argument("fdate", nargs="?", default="")
     ap.add_argument("dsource", nargs="?", default="")
     ap.add_argument("tol", nargs="?", default=None)
+    ap.add_argument("maxresults", nargs="?", default=None, type=int,
+                    help="write only the N most suspicious events under TOL (-1: no limit)")
+    ap.add_argument("--max-results", type=int, default=None, help="as MAXRESULTS; wins over the positional")
     ap.add_argument("--conf", default=knobs.get("ONI_CONF", "/etc/duxbay.conf"))
     ap.add_argument("--lpath")
     ap.add_argument("--flow-path")
@@ -141,6 +146,7 @@ def cmd_ml_ops(argv):
 
     def resolve(world):
         return CFG.resolve(a.fdate, a.dsource, tol=float(a.tol) if a.tol is not None else None, conf_path=a.conf,
+                           max_results=a.max_results if a.max_results is not None else a.maxresults,
                            lpath=a.lpath, flow_path=a.flow_path, dns_path=a.dns_path, top1m=a.top1m,
                            topics=a.topics, alpha=a.alpha, dupfactor=a.dupfactor, gpus=world, backend=a.backend,
                            compat=a.compat, seed=a.seed, start=a.start, resume=a.resume, threads=a.threads,

@@ -26,7 +26,7 @@ from typing import Dict, List, Optional
 from .models.lda.settings import LDASettings
 
 ENV_KEYS = ("FLOW_PATH", "DNS_PATH", "HPATH", "LPATH", "LUSER", "TOL", "DUPFACTOR", "KRB_AUTH", "NODES", "UINODE",
-            "RPATH", "LDAPATH", "SPK_EXEC", "SPK_EXEC_MEM", "TOP1M", "CUT")
+            "RPATH", "LDAPATH", "SPK_EXEC", "SPK_EXEC_MEM", "TOP1M", "CUT", "MAXRESULTS")
 
 _VAR = re.compile(r"\$\{([A-Za-z_][A-Za-z0-9_]*)\}|\$([A-Za-z_][A-Za-z0-9_]*)")
 
@@ -77,6 +77,7 @@ class RunConfig:
     fdate: str = ""
     dsource: str = "flow"                 # flow | dns
     tol: float = 1e-20
+    max_results: int = -1                 # MAXRESULTS: write only the N lowest scores under TOL; -1: no limit
     lpath: str = ""                       # local working dir (reference: ${LUSER}/ml/${FDATE})
     hpath: str = ""                       # HDFS dir in the reference; unused unless set (optional copy target)
     flow_path: str = ""
@@ -137,6 +138,8 @@ class RunConfig:
             raise ValueError("DNS_PATH is not set")
         if self.topics < 1:
             raise ValueError("topics must be >= 1")
+        if self.max_results != -1 and self.max_results < 1:
+            raise ValueError(f"MAXRESULTS must be -1 (no limit) or >= 1, got {self.max_results}")
         return self
 
     def to_dict(self) -> dict:
@@ -145,7 +148,7 @@ class RunConfig:
 
 
 def resolve(fdate: str, dsource: str, tol: Optional[float] = None, conf_path: Optional[str] = None,
-            environ: Optional[Dict[str, str]] = None, **overrides) -> RunConfig:
+            environ: Optional[Dict[str, str]] = None, max_results: Optional[int] = None, **overrides) -> RunConfig:
     """Build a RunConfig from the duxbay file, the environment and explicit overrides."""
     env = dict(os.environ if environ is None else environ)
     cfg = RunConfig(fdate=fdate, dsource=dsource)
@@ -158,6 +161,8 @@ def resolve(fdate: str, dsource: str, tol: Optional[float] = None, conf_path: Op
         _apply(cfg, layer)
     if tol is not None:
         cfg.tol = float(tol)
+    if max_results is not None:
+        cfg.max_results = int(max_results)
     if not cfg.lpath and isinstance(layers[0].get("LUSER") if layers else None, str):
         cfg.lpath = os.path.join(str(layers[0]["LUSER"]), "ml", fdate)
     for k, v in overrides.items():
@@ -179,6 +184,8 @@ def _apply(cfg: RunConfig, layer: Dict[str, object]):
             setattr(cfg, attr, layer[k])
     if "TOL" in layer and layer["TOL"] not in ("", None):
         cfg.tol = float(layer["TOL"])
+    if "MAXRESULTS" in layer and layer["MAXRESULTS"] not in ("", None):
+        cfg.max_results = int(layer["MAXRESULTS"])
     if "DUPFACTOR" in layer and layer["DUPFACTOR"] not in ("", None):
         cfg.dupfactor = int(layer["DUPFACTOR"])
     if "CUT" in layer and isinstance(layer["CUT"], str) and layer["CUT"].strip():

@@ -283,6 +283,48 @@ def score_events(theta, phi, K, dflt, doc_a, word_a, doc_b, word_b, tol):
     return sa, sb, key, flag
 
 
+SELECT_TILE = 2048   # rows of one tile of the selection kernels (csrc/hip/kernels.h kSelectTile)
+
+
+def select_lowest(key, flag, limit, max_blocks: int = 0, with_count: bool = False):
+    """Row indices (int64, ascending) of the ``limit`` flagged rows that a stable ascending sort of their keys
+    puts first -- ``rank_flagged(key, flag)[:limit]`` as a set; all the flagged rows when there are fewer.
+    Keys order as ``sortgroup.f64_order_keys``, ties at the cut go to the lowest row (csrc/hip/select_lowest.hip:
+    a radix select, no sort and no compaction of the flagged rows).  One host read (the count of selected rows).
+    ``max_blocks``: cap on the workgroups per launch (tests: a small cap makes the grid-stride loops wrap).
+    ``with_count``: also return the number of flagged rows."""
+    import operator
+    limit = operator.index(limit)      # TypeError for a float
+    if limit < 1:
+        raise ValueError(f"limit must be >= 1, got {limit}")
+    if not isinstance(max_blocks, int) or max_blocks < 0:
+        raise ValueError(f"max_blocks must be a non-negative int, got {max_blocks!r}")
+    if not isinstance(key, torch.Tensor) or key.dim() != 1:
+        raise ValueError("key: expected a 1-D tensor")
+    n = key.numel()
+    dev = key.device
+    if n >= 1 << 31:
+        raise ValueError(f"select_lowest: {n} rows, the kernels count in 32 bits (n < 2^31)")
+    p_key = _chk(key, torch.float64, "key", (n,), dev)
+    p_flag = _chk(flag, torch.uint8, "flag", (n,), dev)
+    if n == 0:
+        out = torch.empty(0, dtype=torch.int64, device=dev)
+        return (out, 0) if with_count else out
+    L = lib()
+    if L.select_tile() != SELECT_TILE:
+        raise RuntimeError("select_lowest: SELECT_TILE differs from the compiled kSelectTile")
+    cap = min(limit, n)
+    work = torch.empty(int(L.select_work_words(n)), dtype=torch.int32, device=dev)
+    out = torch.empty(cap, dtype=torch.int64, device=dev)
+    L.select_lowest(p_key, p_flag, int(n), int(cap), work.data_ptr(), out.data_ptr(), int(cap), int(max_blocks),
+                    _stream())
+    r = L.select_result_word()
+    flagged, m = (int(x) for x in work[r:r + 2].cpu().tolist())
+    if not 0 <= m <= cap or m != min(cap, flagged):
+        raise RuntimeError(f"select_lowest: inconsistent counts (selected {m}, flagged {flagged}, limit {cap})")
+    return (out[:m], flagged) if with_count else out[:m]
+
+
 def flow_words(hour, minute, second, port_a, port_b, ipkt, ibyt, time_cuts, ibyt_cuts, ipkt_cuts):
     n = hour.numel()
     dev = hour.device

@@ -122,6 +122,41 @@ def score(theta, phi, K, dflt, doc_a, word_a, doc_b=None, word_b=None, tol=float
     return sa, sb, key, (key < tol).to(torch.uint8)
 
 
+def select_lowest(key, flag, limit, with_count: bool = False):
+    """Torch twin of ``ops.hip.select_lowest`` (csrc/hip/select_lowest.hip) on any device: the row indices
+    (int64, ascending) of the ``limit`` flagged rows that a stable ascending sort of their keys puts first, all
+    the flagged rows when there are fewer.  The kernels' plan from the sortgroup helpers: the cut key T is the
+    m-th smallest order key of the flagged rows (m = min(limit, flagged rows)); a row is taken when its key is
+    below T, or equals T with fewer than ``need`` = m - #{below T} flagged rows equal to T ahead of it.
+    ``with_count``: also return the number of flagged rows."""
+    import operator
+
+    from . import sortgroup as SG
+    limit = operator.index(limit)
+    if limit < 1:
+        raise ValueError(f"limit must be >= 1, got {limit}")
+    if key.dim() != 1 or key.dtype != torch.float64 or flag.shape != key.shape:
+        raise ValueError("select_lowest: key float64 [n], flag [n]")
+    n = key.numel()
+    dev = key.device
+    on = flag.reshape(-1).to(torch.bool)
+    rows = torch.arange(n, device=dev, dtype=torch.int64)
+    flagged = int(on.to(torch.int64).sum()) if n else 0
+    m = min(limit, flagged)
+    if m == 0:
+        out = torch.empty(0, dtype=torch.int64, device=dev)
+        return (out, flagged) if with_count else out
+    # unflagged rows sort last: no order key is the largest int64 (f64_order_keys makes every NaN the canonical one)
+    ok = torch.where(on, SG.f64_order_keys(key), torch.full((n,), SG._LOW63, dtype=torch.int64, device=dev))
+    T = SG.sort_stable(ok)[0][m - 1]
+    lt = on & (ok < T)
+    eq = on & (ok == T)
+    need = m - int(lt.to(torch.int64).sum())
+    ahead = torch.cumsum(eq.to(torch.int64), 0) - eq.to(torch.int64)      # flagged rows equal to T before this row
+    out = SG.compact(rows, lt | (eq & (ahead < need)))[0]
+    return (out, flagged) if with_count else out
+
+
 def flow_words(hour, minute, second, port_a, port_b, ipkt, ibyt, time_cuts, ibyt_cuts, ipkt_cuts):
     """Torch transcription of csrc/hip/flow_words.hip (flow_pre_lda.scala:272-358)."""
     t = (hour + minute / 60) + second / 3600

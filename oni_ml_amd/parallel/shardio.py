@@ -498,15 +498,20 @@ def write_segments(ctx, path: str, segs: Sequence[np.ndarray]) -> int:
     return total
 
 
-def merge_sorted_rows(ctx, keys: np.ndarray, text: np.ndarray, row_ends: np.ndarray, path: str) -> int:
+def merge_sorted_rows(ctx, keys: np.ndarray, text: np.ndarray, row_ends: np.ndarray, path: str,
+                      limit: Optional[int] = None) -> int:
     """Write every rank's rows into one file in global ascending key order, ties in rank order then
     local order (one process's stable sort over the rows in input order).  ``keys`` (float64) are
     this rank's row keys, already ascending (stable); ``text`` / ``row_ends`` their formatted lines.
-    Returns the number of rows in the file."""
+    ``limit`` (MAXRESULTS): only the first ``limit`` rows of that order are written -- every rank passes its
+    own lowest ``limit`` rows (the global ones are among them); rows placed past the limit are dropped
+    before the exchange.  Returns the number of rows in the file."""
     from ..ops import native
     keys = np.ascontiguousarray(keys, np.float64)
     N, r = world(ctx), rank(ctx)
     if not _active(ctx):
+        if limit is not None and keys.size > limit >= 1:
+            keys, text = keys[:limit], text[:int(np.asarray(row_ends, np.int64)[limit - 1])]
         write_segments(ctx, path, [text])
         return int(keys.size)
     all_keys = allgather_array(ctx, keys)
@@ -517,6 +522,12 @@ def merge_sorted_rows(ctx, keys: np.ndarray, text: np.ndarray, row_ends: np.ndar
             pos += np.searchsorted(ks, keys, side="right")
         elif s_ > r:
             pos += np.searchsorted(ks, keys, side="left")
+    if limit is not None:
+        # pos ascends with the local rows: the rows kept are a prefix of this rank's
+        kept = int(np.searchsorted(pos, int(limit), side="left"))
+        row_ends = np.asarray(row_ends, np.int64)[:kept]
+        keys, pos, text = keys[:kept], pos[:kept], text[:int(row_ends[-1]) if kept else 0]
+        total = min(total, int(limit))
     # destination: rank d holds global rows [total d / N, total (d + 1) / N)
     bounds = np.asarray([total * d // N for d in range(N + 1)], np.int64)
     dest = np.searchsorted(bounds, pos, side="right") - 1

@@ -201,6 +201,13 @@ def doc_rows_of(doc_keys, n_keys: int) -> np.ndarray:
     return rows
 
 
+def flagged_text(written: int, below_tol: int, limit, what: str, tol) -> str:
+    """The scorers' log line: the rows written, and with a MAXRESULTS limit also the count under TOL."""
+    if limit is None:
+        return f"{written} {what} with score < {tol}"
+    return f"{written} of the {below_tol} {what} with score < {tol} (MAXRESULTS {limit})"
+
+
 def save_json(path: str, obj):
     with open(path, "w") as f:
         json.dump(obj, f, indent=1, default=lambda o: o.tolist() if hasattr(o, "tolist") else str(o))

@@ -126,6 +126,7 @@ def run(cfg, dist=None, device=None, log=print) -> dict:
             with R.stage("dns_post") as res:
                 res.update(score_dns(cfg, tab, top, tables, device, log, host=pre_host))
                 summary["scored"] = res.get("flagged")
+                summary["below_tol"] = res.get("below_tol")
         else:
             R.skip("dns_post")
     except BaseException:
@@ -168,7 +169,12 @@ def score_dns(cfg, tab: FD.DnsTable, top, tables: C.ModelTables, device, log=pri
         raise ValueError("compat=strict scores over exactly 20 topics (dns_post_lda.scala:316)")
     model = S.TopicModel.build(th, ph, S.default_value("dns", K, cfg.strict), device)
     sc, _, key, flag = S.score(model, didx, widx, None, None, cfg.tol)
-    order = S.rank_flagged(key, flag)
+    limit = cfg.max_results if cfg.max_results > 0 else None      # MAXRESULTS: the `limit` lowest scores only
+    if limit is None:
+        order = S.rank_flagged(key, flag)
+        below = int(order.size)
+    else:
+        order, below = S.rank_flagged_counted(key, flag, limit)
     n = int(order.size)
     out = os.path.join(cfg.lpath, "dns_results.csv")
     # the flagged rows' 8 input columns, dictionary-encoded by Arrow on a thread each (its kernels
@@ -192,12 +198,15 @@ def score_dns(cfg, tab: FD.DnsTable, top, tables: C.ModelTables, device, log=pri
     from ..ops import native
     if multi:
         text, ends = native.lib().format_rows(None, cols, n=n, row_ends=True, threads=cfg.threads)
-        total = SIO.merge_sorted_rows(ctx, key[o_t].cpu().numpy().astype(np.float64), text, ends, out)
-        log(f"dns_post: {total} queries with score < {cfg.tol} written to {out} ({n} from rank {ctx.rank})")
-        return dict(flagged=total, rank_flagged=n, events=ctx.allreduce_int(int(feat.word_key.numel())))
+        total = SIO.merge_sorted_rows(ctx, key[o_t].cpu().numpy().astype(np.float64), text, ends, out, limit=limit)
+        below = ctx.allreduce_int(below)
+        log(f"dns_post: {C.flagged_text(total, below, limit, 'queries', cfg.tol)} written to {out} "
+            f"({n} from rank {ctx.rank})")
+        return dict(flagged=total, below_tol=below, rank_flagged=n,
+                    events=ctx.allreduce_int(int(feat.word_key.numel())))
     native.lib().write_rows(out, None, cols, threads=cfg.threads, n=n)
-    log(f"dns_post: {n} queries with score < {cfg.tol} written to {out}")
-    return dict(flagged=n, events=int(feat.word_key.numel()))
+    log(f"dns_post: {C.flagged_text(n, below, limit, 'queries', cfg.tol)} written to {out}")
+    return dict(flagged=n, below_tol=below, events=int(feat.word_key.numel()))
 
 
 def synthetic_dns_corpus(events: int = 2_000_000, seed: int = 0, device=None, strict: bool = True, threads: int = 8,

@@ -172,6 +172,7 @@ def run(cfg, dist=None, device=None, log=print) -> dict:
             with R.stage("flow_post") as res:
                 res.update(score_flow(cfg, ft, tables, device, log, ip_rows=ip_rows))
                 summary["scored"] = res.get("flagged")
+                summary["below_tol"] = res.get("below_tol")
         else:
             R.skip("flow_post")
     except BaseException:
@@ -237,7 +238,12 @@ def score_flow(cfg, ft: FF.FlowTable, tables: C.ModelTables, device, log=print, 
     model = S.TopicModel.build(th, ph, S.default_value("flow", K, cfg.strict), device)
     sa, sb, key, flag = S.score(model, SG.gather(didx, feat.sip), w_src, SG.gather(didx, feat.dip), w_dst, cfg.tol)
     qs = S.key_quantiles(key)
-    order = S.rank_flagged(key, flag)
+    limit = cfg.max_results if cfg.max_results > 0 else None      # MAXRESULTS: the `limit` lowest scores only
+    if limit is None:
+        order = S.rank_flagged(key, flag)
+        below = int(order.size)
+    else:
+        order, below = S.rank_flagged_counted(key, flag, limit)
     n = int(order.size)
     out = os.path.join(cfg.lpath, "flow_results.csv")
     # output columns: 27 raw + time + ibyt_bin + ipkt_bin + time_bin + word_port + ip_pair + src/dest word + scores
@@ -266,12 +272,15 @@ def score_flow(cfg, ft: FF.FlowTable, tables: C.ModelTables, device, log=print, 
     from ..ops import native
     if multi:
         text, ends = native.lib().format_rows(None, cols, n=n, row_ends=True, threads=cfg.threads)
-        total = SIO.merge_sorted_rows(ctx, sel(key).astype(np.float64), text, ends, out)
-        log(f"flow_post: {total} events with score < {cfg.tol} written to {out} ({n} from rank {ctx.rank})")
-        return dict(flagged=total, rank_flagged=n, events=ctx.allreduce_int(int(feat.time.numel())), **qs)
+        total = SIO.merge_sorted_rows(ctx, sel(key).astype(np.float64), text, ends, out, limit=limit)
+        below = ctx.allreduce_int(below)
+        log(f"flow_post: {C.flagged_text(total, below, limit, 'events', cfg.tol)} written to {out} "
+            f"({n} from rank {ctx.rank})")
+        return dict(flagged=total, below_tol=below, rank_flagged=n,
+                    events=ctx.allreduce_int(int(feat.time.numel())), **qs)
     native.lib().write_rows(out, None, cols, threads=cfg.threads, n=n)
-    log(f"flow_post: {n} events with score < {cfg.tol} written to {out}")
-    return dict(flagged=n, events=int(feat.time.numel()), **qs)
+    log(f"flow_post: {C.flagged_text(n, below, limit, 'events', cfg.tol)} written to {out}")
+    return dict(flagged=n, below_tol=below, events=int(feat.time.numel()), **qs)
 
 
 def synthetic_flow_corpus(events: int = 1_000_000, seed: int = 0, workdir: Optional[str] = None, device=None,

@@ -143,6 +143,7 @@ def run_flow(cfg, ctx, device=None, log=print) -> dict:
                 res.update(score_flow(cfg, ft, tables, device, log if rank0 else (lambda *a, **k: None),
                                       ctx=ctx, ip_rows=ip_rows))
                 summary["scored"] = res.get("flagged")
+                summary["below_tol"] = res.get("below_tol")
         else:
             R.skip("flow_post")
     except BaseException:
@@ -201,6 +202,7 @@ def run_dns(cfg, ctx, device=None, log=print) -> dict:
                 res.update(score_dns(cfg, tab, top, tables, device, log if rank0 else (lambda *a, **k: None),
                                      ctx=ctx, ip_map=ip_rows))
                 summary["scored"] = res.get("flagged")
+                summary["below_tol"] = res.get("below_tol")
         else:
             R.skip("dns_post")
     except BaseException:

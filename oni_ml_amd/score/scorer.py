@@ -67,14 +67,41 @@ def key_quantiles(key: torch.Tensor, qs=(1e-4, 1e-3, 1e-2, 0.1, 0.5), sample: in
     return {f"key_q{q:g}": float(x) for q, x in zip(qs, v)}
 
 
-def rank_flagged(key: torch.Tensor, flag: torch.Tensor) -> torch.Tensor:
-    """Indices of flagged rows in ascending key order (stable) as an int64 host array."""
+def rank_flagged(key: torch.Tensor, flag: torch.Tensor, limit: Optional[int] = None) -> torch.Tensor:
+    """Indices of flagged rows in ascending key order (stable) as an int64 host array.
+
+    ``limit`` (MAXRESULTS): only the first ``limit`` of them, element for element ``rank_flagged(key, flag)[:limit]``
+    -- see ``rank_flagged_counted``."""
+    if limit is not None:
+        return rank_flagged_counted(key, flag, limit)[0]
     from ..ops import sortgroup as SG
     sel, _ = SG.compact(torch.arange(flag.numel(), device=flag.device), flag.reshape(-1).to(torch.bool))
     if sel.numel() == 0:
         return np.zeros(0, np.int64)
     order = SG.sort_stable(SG.gather(key, sel))[1]
     return SG.gather(sel, order).cpu().numpy().astype(np.int64)
+
+
+def rank_flagged_counted(key: torch.Tensor, flag: torch.Tensor, limit: int):
+    """(``rank_flagged(key, flag)[:limit]``, number of flagged rows) without ranking every flagged row: the
+    ``limit`` lowest are selected first (the HIP radix select ``ops.hip.select_lowest`` on the GPU, its torch
+    twin elsewhere; ties at the cut to the lowest row), then only those m <= limit keys are sorted.  The
+    selection arrives in row order, so the stable sort orders ties as the full sort does.  Always selects: on an
+    MI355X it was 1.8 - 3.0 x faster than ranking everything at every shape measured (2 M rows with N = 3,000 and
+    100,000, 100 M rows with N = 3,000: profiles/select_lowest.md), so there is no fall-back rule."""
+    from ..ops import sortgroup as SG
+    flag = flag.reshape(-1)
+    if key.device.type == "cuda":
+        from ..ops import hip as H
+        sel, flagged = H.select_lowest(key.reshape(-1).contiguous(), flag.to(torch.uint8).contiguous(), limit,
+                                       with_count=True)
+    else:
+        from ..ops.reference import select_lowest
+        sel, flagged = select_lowest(key.reshape(-1), flag, limit, with_count=True)
+    if sel.numel() == 0:
+        return np.zeros(0, np.int64), flagged
+    order = SG.sort_stable(SG.gather(key, sel))[1]
+    return SG.gather(sel, order).cpu().numpy().astype(np.int64), flagged
 
 
 def lookup_sorted(keys_sorted: torch.Tensor, values_idx: torch.Tensor, query: torch.Tensor) -> torch.Tensor:

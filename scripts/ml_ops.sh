@@ -1,5 +1,5 @@
 #!/bin/bash
-# Drop-in for the reference ml_ops.sh (YYYYMMDD TYPE [TOL]); extra flags pass through.
+# Drop-in for the reference ml_ops.sh (YYYYMMDD TYPE [TOL] [MAXRESULTS]); extra flags pass through.
 # GPUs: ONI_GPUS=N runs one process per GPU under torchrun (RCCL over xGMI).
 HERE="$(cd "$(dirname "${BASH_SOURCE[0]}")/.." && pwd)"
 export PYTHONPATH="${HERE}${PYTHONPATH:+:${PYTHONPATH}}"
