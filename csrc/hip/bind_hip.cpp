@@ -165,6 +165,14 @@ PYBIND11_MODULE(_onihip, m) {
     oni::launch_select_lowest(a, max_blocks, S(stream));
   });
 
+  m.def("string_entropy", [](u bytes, u offsets, int64_t n, u table, int64_t table_len, u out, int max_blocks,
+                             u stream) {
+    if (n < 0 || table_len < 2 || max_blocks < 0) throw std::runtime_error("string_entropy: bad sizes");
+    oni::StringEntropyArgs a{P<const uint8_t>(bytes), P<const int64_t>(offsets), n, P<const double>(table),
+                             table_len, P<double>(out)};
+    oni::launch_string_entropy(a, max_blocks, S(stream));
+  });
+
   m.def("flow_words", [](u hour, u minute, u second, u port_a, u port_b, u ipkt, u ibyt, u time_cuts,
                          int n_time, u ibyt_cuts, int n_ibyt, u ipkt_cuts, int n_ipkt, int64_t n, u time_out,
                          u time_bin, u ibyt_bin, u ipkt_bin, u word_port, u p_case, u src_prefix,

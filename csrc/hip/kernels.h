@@ -247,6 +247,19 @@ int select_result_word();
 // max_blocks: cap on the workgroups per launch (0: 2048); more tiles than that are grid-strided
 void launch_select_lowest(const SelectArgs& a, int max_blocks, hipStream_t s);
 
+// Byte entropy of every string of a batch (string_entropy.hip): out[i] = (t[n] - sum_b t[c_b]) / n over the
+// bytes [offsets[i], offsets[i + 1]) of `bytes`, t = table (c log2 c, host-built), 0 for n <= 1.
+struct StringEntropyArgs {
+  const uint8_t* bytes;     // [offsets[n]] at any alignment; nothing outside a string's range is loaded
+  const int64_t* offsets;   // [n + 1] non-decreasing, inside the bytes buffer (checked on the host)
+  int64_t n;                // strings
+  const double* table;      // [table_len], table_len > the longest string's length
+  int64_t table_len;
+  double* out;              // [n]
+};
+// max_blocks: cap on the workgroups (0: 4096); more strings than the grid's waves are grid-strided
+void launch_string_entropy(const StringEntropyArgs& a, int max_blocks, hipStream_t s);
+
 // ------------------------------------------------------------ flow words ---
 struct FlowWordArgs {
   const double* hour;      // [n] col 4

@@ -1,6 +1,6 @@
 """Command line: ``python -m oni_ml_amd <command> ...`` (and scripts/ml_ops.sh).
 
-  ml_ops YYYYMMDD {flow|dns} [TOL] [MAXRESULTS] [options]
+  ml_ops YYYYMMDD {flow|dns|proxy} [TOL] [MAXRESULTS] [options]
                                                end-to-end run (reference ml_ops.sh:1-123); MAXRESULTS: only the
                                                N lowest scores under TOL are written (-1: no limit)
   lda est <alpha> <k> <settings> <nproc> <corpus> <random|seeded|prefix> <dir>
@@ -8,7 +8,7 @@
   lda inf <settings> <model-prefix> <corpus> <name>
   lda_pre <LPATH>/                             lda_pre.py equivalent (doc_wc.dat -> words/doc/model.dat)
   lda_post <LPATH>/                            lda_post.py equivalent (final.* -> doc/word_results.csv)
-  synth {flow|dns} --out DIR ...               synthetic inputs (flow CSV day, DNS parquet, top-1m.csv)
+  synth {flow|dns|proxy} --out DIR ...         synthetic inputs (flow CSV day, DNS / proxy parquet, top-1m.csv)
   qtiles [show] <flow_qtiles>                  print cuts of the legacy qtiles format
   qtiles gen <FLOW_PATH> [--out DIR]           gen_qtiles.sh + qtiles.py: sample ntile cuts -> flow_qtiles
   install [--nodes a,b] [--dry-run]            install_ml.sh: rsync the framework to NODES:${LUSER}/ml
@@ -111,6 +111,7 @@ def cmd_ml_ops(argv):
     ap.add_argument("--lpath")
     ap.add_argument("--flow-path")
     ap.add_argument("--dns-path")
+    ap.add_argument("--proxy-path", help="one or more comma-separated parquet paths (PROXY_PATH)")
     ap.add_argument("--top1m")
     ap.add_argument("--topics", type=int, default=20)
     ap.add_argument("--alpha", type=float, default=2.5)
@@ -143,11 +144,14 @@ def cmd_ml_ops(argv):
     # stages' kernels while the inputs parse, were both measured slower and removed in round 5:
     # profiles/r4_cold_start.md, profiles/r4_tuning_log.md §3)
     from . import config as CFG
+    if a.dsource == "proxy" and (a.gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1 or a.hdfs):
+        raise ValueError(CFG.PROXY_ONE_PROCESS)     # before a process group is asked for
 
     def resolve(world):
         return CFG.resolve(a.fdate, a.dsource, tol=float(a.tol) if a.tol is not None else None, conf_path=a.conf,
                            max_results=a.max_results if a.max_results is not None else a.maxresults,
-                           lpath=a.lpath, flow_path=a.flow_path, dns_path=a.dns_path, top1m=a.top1m,
+                           lpath=a.lpath, flow_path=a.flow_path, dns_path=a.dns_path, proxy_path=a.proxy_path,
+                           top1m=a.top1m,
                            topics=a.topics, alpha=a.alpha, dupfactor=a.dupfactor, gpus=world, backend=a.backend,
                            compat=a.compat, seed=a.seed, start=a.start, resume=a.resume, threads=a.threads,
                            write_doc_wc=a.keep_doc_wc, word_assignments=a.word_assignments,
@@ -311,7 +315,7 @@ def cmd_lda_post(argv):
 
 def cmd_synth(argv):
     ap = argparse.ArgumentParser(prog="synth")
-    ap.add_argument("kind", choices=["flow", "dns"])
+    ap.add_argument("kind", choices=["flow", "dns", "proxy"])
     ap.add_argument("--out", required=True)
     ap.add_argument("--events", type=int, default=1_000_000)
     ap.add_argument("--files", type=int, default=1)
@@ -320,9 +324,13 @@ def cmd_synth(argv):
     if a.kind == "flow":
         from .synth.flow import generate_flow_day
         print(generate_flow_day(a.out, a.events, a.seed, files=a.files))
-    else:
+    elif a.kind == "dns":
         from .synth.dns import generate_dns_day
         print(generate_dns_day(a.out, a.events, a.seed, files=a.files))
+    else:
+        from .synth.proxy import generate_proxy_day
+        r = generate_proxy_day(a.out, a.events, a.seed, files=a.files)
+        print({k: (v if k not in ("planted", "planted_kinds") else len(v)) for k, v in r.items()})
     return 0
 
 

@@ -25,8 +25,11 @@ from typing import Dict, List, Optional
 
 from .models.lda.settings import LDASettings
 
-ENV_KEYS = ("FLOW_PATH", "DNS_PATH", "HPATH", "LPATH", "LUSER", "TOL", "DUPFACTOR", "KRB_AUTH", "NODES", "UINODE",
-            "RPATH", "LDAPATH", "SPK_EXEC", "SPK_EXEC_MEM", "TOP1M", "CUT", "MAXRESULTS")
+ENV_KEYS = ("FLOW_PATH", "DNS_PATH", "PROXY_PATH", "HPATH", "LPATH", "LUSER", "TOL", "DUPFACTOR", "KRB_AUTH", "NODES",
+            "UINODE", "RPATH", "LDAPATH", "SPK_EXEC", "SPK_EXEC_MEM", "TOP1M", "CUT", "MAXRESULTS")
+
+# proxy has no multi-rank, sharded or HDFS-staged form
+PROXY_ONE_PROCESS = "proxy runs on one process: launch it without torchrun, with --gpus 1 and without --hdfs"
 
 _VAR = re.compile(r"\$\{([A-Za-z_][A-Za-z0-9_]*)\}|\$([A-Za-z_][A-Za-z0-9_]*)")
 
@@ -75,13 +78,14 @@ def run_vars(fdate: str, dsource: str) -> Dict[str, str]:
 @dataclass
 class RunConfig:
     fdate: str = ""
-    dsource: str = "flow"                 # flow | dns
+    dsource: str = "flow"                 # flow | dns | proxy
     tol: float = 1e-20
     max_results: int = -1                 # MAXRESULTS: write only the N lowest scores under TOL; -1: no limit
     lpath: str = ""                       # local working dir (reference: ${LUSER}/ml/${FDATE})
     hpath: str = ""                       # HDFS dir in the reference; unused unless set (optional copy target)
     flow_path: str = ""
     dns_path: str = ""
+    proxy_path: str = ""                  # one or more comma-separated parquet paths
     top1m: str = "top-1m.csv"
     dupfactor: int = 1000
     topics: int = 20
@@ -124,8 +128,8 @@ class RunConfig:
         return os.path.join(self.lpath, f"{self.dsource}_scores.csv")
 
     def validate(self):
-        if self.dsource not in ("flow", "dns"):
-            raise ValueError("TYPE must be flow or dns")
+        if self.dsource not in ("flow", "dns", "proxy"):
+            raise ValueError("TYPE must be flow, dns or proxy")
         if self.fdate and (len(self.fdate) != 8 or not self.fdate.isdigit()):
             raise ValueError("FDATE must be YYYYMMDD")
         if self.compat not in ("strict", "fixed"):
@@ -136,6 +140,11 @@ class RunConfig:
             raise ValueError("FLOW_PATH is not set")
         if self.dsource == "dns" and not self.dns_path:
             raise ValueError("DNS_PATH is not set")
+        if self.dsource == "proxy":
+            if not self.proxy_path:
+                raise ValueError("PROXY_PATH is not set")
+            if self.gpus > 1 or self.hdfs:
+                raise ValueError(PROXY_ONE_PROCESS)
         if self.topics < 1:
             raise ValueError("topics must be >= 1")
         if self.max_results != -1 and self.max_results < 1:
@@ -178,7 +187,8 @@ def resolve(fdate: str, dsource: str, tol: Optional[float] = None, conf_path: Op
 
 
 def _apply(cfg: RunConfig, layer: Dict[str, object]):
-    m = dict(FLOW_PATH="flow_path", DNS_PATH="dns_path", HPATH="hpath", LPATH="lpath", TOP1M="top1m")
+    m = dict(FLOW_PATH="flow_path", DNS_PATH="dns_path", PROXY_PATH="proxy_path", HPATH="hpath", LPATH="lpath",
+             TOP1M="top1m")
     for k, attr in m.items():
         if k in layer and isinstance(layer[k], str) and layer[k]:
             setattr(cfg, attr, layer[k])

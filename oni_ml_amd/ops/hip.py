@@ -325,6 +325,49 @@ def select_lowest(key, flag, limit, max_blocks: int = 0, with_count: bool = Fals
     return (out[:m], flagged) if with_count else out[:m]
 
 
+def string_entropy(bytes_u8, offsets, max_blocks: int = 0):
+    """float64 [n] Shannon entropy of the byte strings [offsets[i], offsets[i + 1]) of ``bytes_u8`` (uint8, on
+    the GPU), bit for bit ``ops.reference.string_entropy`` (csrc/hip/string_entropy.hip).  ``offsets``: int64
+    [n + 1] on the host, where they come from (Arrow) and where they are checked before the launch:
+    non-decreasing, first >= 0, last <= bytes_u8.numel(); device offsets are refused instead of being copied back
+    on every call.  ``max_blocks``: cap on the workgroups (tests: a small cap makes the grid-stride loop wrap).
+    The kernel reads the ``entropy_table`` of the longest string of the call."""
+    from .reference import entropy_table
+    if not isinstance(max_blocks, int) or max_blocks < 0:
+        raise ValueError(f"max_blocks must be a non-negative int, got {max_blocks!r}")
+    if not isinstance(bytes_u8, torch.Tensor) or bytes_u8.dim() != 1:
+        raise ValueError("bytes: expected a 1-D tensor")
+    if not isinstance(offsets, torch.Tensor) or offsets.dim() != 1 or offsets.numel() < 1:
+        raise ValueError("offsets: expected a 1-D tensor of n + 1 entries")
+    if offsets.dtype != torch.int64:
+        raise TypeError(f"offsets: expected {torch.int64}, got {offsets.dtype}")
+    if offsets.is_cuda:
+        raise ValueError("offsets: expected on the host (they are checked there, then uploaded)")
+    dev = bytes_u8.device
+    p_bytes = _chk(bytes_u8, torch.uint8, "bytes", None, dev)
+    n = offsets.numel() - 1
+    off_h = offsets
+    if n:
+        d = off_h[1:] - off_h[:-1]
+        if int(d.min()) < 0:
+            raise ValueError("offsets: must be non-decreasing")
+    if int(off_h[0]) < 0 or int(off_h[-1]) > bytes_u8.numel():
+        raise ValueError(f"offsets: [{int(off_h[0])}, {int(off_h[-1])}] outside the {bytes_u8.numel()} bytes")
+    out = torch.empty(n, dtype=torch.float64, device=dev)
+    if n == 0:
+        return out
+    longest = int(d.max())
+    if longest >= 1 << 31:
+        raise ValueError(f"string_entropy: a string of {longest} bytes, the kernel counts in 32 bits")
+    table = torch.from_numpy(entropy_table(longest)).to(dev)      # longest + 1 >= 2 entries
+    p_tab = _chk(table, torch.float64, "table", (longest + 1 if longest >= 1 else 2,), dev)
+    off_d = offsets.to(dev)
+    p_off = _chk(off_d, torch.int64, "offsets", (n + 1,), dev)
+    lib().string_entropy(p_bytes, p_off, int(n), p_tab, int(table.numel()), out.data_ptr(), int(max_blocks),
+                         _stream())
+    return out
+
+
 def flow_words(hour, minute, second, port_a, port_b, ipkt, ibyt, time_cuts, ibyt_cuts, ipkt_cuts):
     n = hour.numel()
     dev = hour.device

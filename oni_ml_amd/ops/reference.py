@@ -157,6 +157,75 @@ def select_lowest(key, flag, limit, with_count: bool = False):
     return (out, flagged) if with_count else out
 
 
+def entropy_table(max_len: int):
+    """t[c] = c log2(c) for c = 0 .. max_len as float64 (t[0] = t[1] = 0): the one table both
+    ``string_entropy`` here and the HIP kernel (csrc/hip/string_entropy.hip) read, so neither side's log
+    enters the comparison.  At least two entries."""
+    import numpy as np
+    c = np.arange(max(int(max_len), 1) + 1, dtype=np.float64)
+    t = np.zeros_like(c)
+    t[2:] = c[2:] * np.log2(c[2:])
+    return t
+
+
+ENTROPY_CHUNK_ROWS = 1 << 14     # rows per count matrix of string_entropy (x 256 int64: 32 MB)
+ENTROPY_CHUNK_BYTES = 1 << 26    # and at most this many bytes per chunk (a row longer than it is a chunk)
+
+
+def string_entropy(data, offsets, table=None):
+    """Numpy twin of ``ops.hip.string_entropy`` (csrc/hip/string_entropy.hip), bit for bit: the Shannon entropy
+    H = (t[n] - sum_b t[c_b]) / n of the bytes [offsets[i], offsets[i + 1]) of ``data`` (anything with the
+    buffer protocol, or a uint8 array / tensor) for every i, float64 [len(offsets) - 1]; 0 for n <= 1.
+    t = ``entropy_table`` of the longest string, c_b the count of the (unsigned) byte value b.
+
+    Summation order (the kernel's): the 256 terms t[c_b] are taken in ascending byte value in 64 groups of
+    four, each group summed left to right, ((t[c_4l] + t[c_4l+1]) + t[c_4l+2]) + t[c_4l+3]; the 64 group sums
+    are then added as a balanced binary tree, neighbours first (x_0 + x_1, x_2 + x_3, ..., six levels).  Absent
+    bytes contribute an exact +0.0.
+
+    Rows are processed in chunks (ENTROPY_CHUNK_ROWS rows or ENTROPY_CHUNK_BYTES bytes, whichever is fewer
+    rows), so a million rows never build an n x 256 matrix at once."""
+    import numpy as np
+    if torch.is_tensor(data):
+        data = data.cpu().numpy()
+    if torch.is_tensor(offsets):
+        offsets = offsets.cpu().numpy()
+    buf = np.frombuffer(data, dtype=np.uint8) if not isinstance(data, np.ndarray) else data.reshape(-1).view(np.uint8)
+    off = np.asarray(offsets, np.int64).reshape(-1)
+    n = off.size - 1
+    if n < 0:
+        raise ValueError("string_entropy: offsets must have n + 1 entries")
+    out = np.zeros(max(n, 0), np.float64)
+    if n == 0:
+        return out
+    lens = np.diff(off)
+    if off[0] < 0 or (lens < 0).any() or off[-1] > buf.size:
+        raise ValueError("string_entropy: offsets must be non-decreasing inside the bytes buffer")
+    t = entropy_table(int(lens.max())) if table is None else np.asarray(table, np.float64)
+    if t.size <= int(lens.max()):
+        raise ValueError("string_entropy: the table is shorter than the longest string")
+    lo = 0
+    while lo < n:
+        hi = min(n, lo + ENTROPY_CHUNK_ROWS)
+        if off[hi] - off[lo] > ENTROPY_CHUNK_BYTES:
+            hi = max(lo + 1, int(np.searchsorted(off, off[lo] + ENTROPY_CHUNK_BYTES, side="right")) - 1)
+        m = hi - lo
+        b0, b1 = int(off[lo]), int(off[hi])
+        row = np.repeat(np.arange(m, dtype=np.int64), lens[lo:hi])
+        cnt = np.bincount(row * 256 + buf[b0:b1], minlength=m * 256).reshape(m, 64, 4)
+        x = t[cnt]
+        s = ((x[:, :, 0] + x[:, :, 1]) + x[:, :, 2]) + x[:, :, 3]
+        while s.shape[1] > 1:
+            s = s[:, 0::2] + s[:, 1::2]
+        ln = lens[lo:hi]
+        big = ln > 1
+        h = np.zeros(m, np.float64)
+        h[big] = (t[ln[big]] - s[big, 0]) / ln[big].astype(np.float64)
+        out[lo:hi] = h
+        lo = hi
+    return out
+
+
 def flow_words(hour, minute, second, port_a, port_b, ipkt, ibyt, time_cuts, ibyt_cuts, ipkt_cuts):
     """Torch transcription of csrc/hip/flow_words.hip (flow_pre_lda.scala:272-358)."""
     t = (hour + minute / 60) + second / 3600

@@ -1,10 +1,13 @@
-"""End-to-end suspicious-connects pipelines (flow / dns), the ml_ops.sh replacement."""
+"""End-to-end suspicious-connects pipelines (flow / dns / proxy), the ml_ops.sh replacement."""
 from __future__ import annotations
 
 
 def run(cfg, dist=None, device=None, log=print) -> dict:
     cfg.validate()
     import os
+    if cfg.dsource == "proxy":     # one process, no HDFS staging (pipeline/proxy.py raises for either)
+        from .proxy import run as _run
+        return _run(cfg, dist=dist, device=device, log=log)
     if dist is None or dist.rank == 0:
         os.makedirs(cfg.lpath, exist_ok=True)
     rank0 = dist is None or dist.rank == 0

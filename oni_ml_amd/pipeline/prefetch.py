@@ -217,7 +217,8 @@ def load_flow_inputs(flow_path, feedback_path, dupfactor, threads=8, fixed_cuts=
 def start_for(cfg, fork: bool = True, after_import: bool = False) -> None:
     """Start the read of ``cfg``'s inputs (flow or dns).  ``fork=False`` (a profiler or tracer whose
     preloaded library may already hold the GPU, cli._tool_attached): the DNS read runs on a thread.
-    ``after_import``: the flow cuts wait for ``imported()`` (the caller imports torch meanwhile)."""
+    ``after_import``: the flow cuts wait for ``imported()`` (the caller imports torch meanwhile).
+    Any other source (proxy) has no prefetch: nothing is started and its load stage reads the day."""
     if cfg.dsource == "flow":
         start(flow_key(cfg), load_flow_inputs, cfg.flow_path, cfg.feedback_path(), cfg.dupfactor, cfg.threads,
               cfg.fixed_cuts() is not None, after_import)

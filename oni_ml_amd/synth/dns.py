@@ -56,6 +56,15 @@ def make_names(rng, n_unique: int):
     return names
 
 
+def write_top1m(path: str) -> str:
+    """The synthetic top-1m.csv (`rank,domain`) in directory ``path``; returns its file name."""
+    top = os.path.join(path, "top-1m.csv")
+    with open(top, "w") as f:
+        for r, dname in enumerate(POPULAR[:20] + ["example", "intel"], start=1):
+            f.write(f"{r},{dname}.com\n")
+    return top
+
+
 def generate_dns_day(path: str, events: int = 100_000, seed: int = 0, files: int = 1, n_names: int = 20_000,
                      n_clients: int = 5_000, date=(2016, 1, 22), with_edge_rows: bool = True) -> dict:
     import pyarrow as pa
@@ -111,8 +120,5 @@ def generate_dns_day(path: str, events: int = 100_000, seed: int = 0, files: int
         p = os.path.join(d, "part-00000.parquet")
         pq.write_table(table.slice(bounds[i], bounds[i + 1] - bounds[i]), p)
         paths.append(d)
-    top = os.path.join(path, "top-1m.csv")
-    with open(top, "w") as f:
-        for r, dname in enumerate(POPULAR[:20] + ["example", "intel"], start=1):
-            f.write(f"{r},{dname}.com\n")
+    top = write_top1m(path)
     return dict(paths=paths, dns_path=",".join(paths), top1m=top, events=events)
