@@ -73,14 +73,17 @@ PYBIND11_MODULE(_onihip, m) {
   m.def("gs_tiny_max", [](int KS) { return oni::gs_tiny_max(KS); });
   m.def("gs_estep", [](u doc_ptr, u word_idx, u counts, u order, int n_items, u beta, int K, int KS, int gs_updates,
                        u params, u gamma, u cphi, u lik, u alpha_ss, u iters, int variant, u stream, u dbg,
-                       u stage, u stage_off) {
+                       u stage, u stage_off, u csum, u et) {
     oni::GSArgs a{P<const int>(doc_ptr), P<const int>(word_idx), P<const float>(counts), P<const int>(order),
                   n_items,               P<const double>(beta),  K,                      gs_updates,
                   P<const double>(params), P<double>(gamma),     P<double>(cphi),        P<double>(lik),
                   P<double>(alpha_ss),   P<int>(iters),         P<long long>(dbg),      P<const double>(stage),
-                  P<const long long>(stage_off)};
+                  P<const long long>(stage_off), P<const double>(csum), P<double>(et)};
     oni::launch_gs_estep(a, variant, KS, S(stream));
-  });
+  }, py::arg("doc_ptr"), py::arg("word_idx"), py::arg("counts"), py::arg("order"), py::arg("n_items"),
+     py::arg("beta"), py::arg("K"), py::arg("KS"), py::arg("gs_updates"), py::arg("params"), py::arg("gamma"),
+     py::arg("cphi"), py::arg("lik"), py::arg("alpha_ss"), py::arg("iters"), py::arg("variant"), py::arg("stream"),
+     py::arg("dbg"), py::arg("stage"), py::arg("stage_off"), py::arg("csum") = (u)0, py::arg("et") = (u)0);
   m.def("gs_stage", [](u beta, u word_idx, u tile_ent, u tile_cnt, int n_tiles, u stage, int KS, u gate, u stream) {
     oni::launch_gs_stage(P<const double>(beta), P<const int>(word_idx), P<const int>(tile_ent),
                          P<const int>(tile_cnt), n_tiles, P<double>(stage), KS, P<const double>(gate), S(stream));
@@ -106,12 +109,18 @@ PYBIND11_MODULE(_onihip, m) {
     oni::launch_gs_split(a, s, KS, S(stream));
   });
   m.def("gs_suff64", [](u word_ptr, u csc_ent, u order, int n_heavy, int n_medium, int n_light, u cphi, u cw, u part,
-                        u lik, u ass, int lo, int hi, int KS, u gate, u stream, u cw_base) {
+                        u lik, u ass, int lo, int hi, int KS, u gate, u stream, u cw_base, u rc_beta, u rc_et,
+                        u rc_et_row, u rc_counts) {
+    const oni::SuffRecompArgs rc{P<const double>(rc_beta), P<const double>(rc_et), P<const int>(rc_et_row),
+                                 P<const float>(rc_counts)};
     oni::launch_gs_suff64(P<const int>(word_ptr), P<const int>(csc_ent), P<const int>(order), n_heavy, n_medium,
                           n_light, P<const double>(cphi), P<double>(cw), P<double>(part), P<const double>(lik),
                           P<const double>(ass), lo, hi, KS, P<const double>(gate), S(stream),
-                          P<const double>(cw_base));
-  });
+                          P<const double>(cw_base), rc);
+  }, py::arg("word_ptr"), py::arg("csc_ent"), py::arg("order"), py::arg("n_heavy"), py::arg("n_medium"),
+     py::arg("n_light"), py::arg("cphi"), py::arg("cw"), py::arg("part"), py::arg("lik"), py::arg("ass"),
+     py::arg("lo"), py::arg("hi"), py::arg("KS"), py::arg("gate"), py::arg("stream"), py::arg("cw_base"),
+     py::arg("rc_beta") = (u)0, py::arg("rc_et") = (u)0, py::arg("rc_et_row") = (u)0, py::arg("rc_counts") = (u)0);
   m.def("gs_mstep_control", [](u cw, u class_total, u beta, int V, int K, int KS, u scalars, u params, u ctl,
                                u hist, int hist_slots, u done_count, u stream, u rows, int n_rows, int newton,
                                int estimate, double num_docs, u alpha_out, u st_word_idx,

@@ -204,6 +204,40 @@ __device__ __forceinline__ double bits_sum(double x) {
   }
 }
 
+// One corpus entry's c*phi values: out_k = E_k b_k r, r = c / P, P = (p0 + p1) + (p2 + p3) with p_i the fma
+// chain over the topics i, i + 4, ... of the row.  The one definition of the final pass, so that a row written
+// by the longest-document kernel and the same row recomputed by the suff-stats pass (gs_suff64 RECOMP) agree
+// bitwise.  TGL = 1: the lane holds the whole row (N = KS values, topic = index).  TGL = 4: the lanes q of a
+// quad hold topics q + 4 i (N = KS / 4): lane q's one chain is p_q, and the two symmetric quad exchanges leave
+// (p0 + p1) + (p2 + p3) in every lane with the same bits (a + b == b + a); the whole quad must be active.
+template <int N, int TGL>
+__device__ __forceinline__ void cphi_row(const double (&E)[N], const double (&b)[N], double c, double (&out)[N]) {
+  // the products below are rounded as written: a caller that adds out_k to a sum must not fuse that add
+  // with the last product (the materialised rows are rounded before they are stored)
+#pragma clang fp contract(off)
+  static_assert(TGL == 1 || TGL == 4, "cphi_row: the whole row or a quad of lanes");
+  double P;
+  if constexpr (TGL == 1) {
+    double p0 = 0.0, p1 = 0.0, p2 = 0.0, p3 = 0.0;
+#pragma unroll
+    for (int kk = 0; kk < N; kk += 4) {
+      p0 = fma(E[kk], b[kk], p0);
+      if (kk + 1 < N) p1 = fma(E[kk + 1], b[kk + 1], p1);
+      if (kk + 2 < N) p2 = fma(E[kk + 2], b[kk + 2], p2);
+      if (kk + 3 < N) p3 = fma(E[kk + 3], b[kk + 3], p3);
+    }
+    P = (p0 + p1) + (p2 + p3);
+  } else {
+    double p = 0.0;
+#pragma unroll
+    for (int i = 0; i < N; ++i) p = fma(E[i], b[i], p);
+    P = xsum<2>(xsum<1>(p));
+  }
+  const double r = c * drcp(P);
+#pragma unroll
+  for (int i = 0; i < N; ++i) out[i] = E[i] * b[i] * r;
+}
+
 __device__ __forceinline__ double params_vconv(const double* p) { return (double)(float)p[3]; }
 
 // lda-c: converged = (L_old - L) / L_old; the loop runs while converged > VAR_CONVERGED

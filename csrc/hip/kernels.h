@@ -124,6 +124,13 @@ struct GSArgs {
   // wave's 64 consecutive words are 16-byte-contiguous per topic pair; stage_off[i] < 0: not staged
   const double* stage = nullptr;
   const long long* stage_off = nullptr;
+  // optional chunk count sums (gs_wsteam): csum[i * kGsUMax + j] = sum of the counts of chunk j of item i's
+  // document, built once per plan on the host (constants of the corpus); nullptr: the kernel sums the counts
+  const double* csum = nullptr;
+  // optional deferred final pass (gs_wsteam): when set, the workgroup of item i leaves the E of every chunk's
+  // final sweep in et[(i * kGsUMax + j) * KS + k] and writes no c*phi rows; the suff-stats pass recomputes
+  // them (launch_gs_suff64 with SuffRecompArgs)
+  double* et = nullptr;
 };
 void launch_gs_estep(const GSArgs& a, int variant, int KS, hipStream_t s);
 // stage[(t KS/2 + k) 64 + l] (double2) = beta row pair k of the word at corpus entry tile_ent[t] + l
@@ -167,10 +174,20 @@ int gs_xsplit_rows(int KS);   // LDS row capacity of one member (its words over 
 
 // class_word[w] = sum over w's CSC entries of cphi rows (fixed order, no atomics); part
 // [nb][2 + KS] per-workgroup {lik slice, alpha_ss slice, column sums} for colsum_partials.
+// Recompute mode (KS <= 32, et != nullptr): the row of CSC slot s is not loaded from cphi but computed as the
+// longest-document kernel's final pass would have written it (gs_math.h cphi_row, bitwise the same): the beta
+// row of the word, the chunk's final-sweep E at et[et_row[s] * KS] (GSArgs::et) and counts[csc_ent[s]].
+struct SuffRecompArgs {
+  const double* beta = nullptr;    // [V][KS]
+  const double* et = nullptr;      // [n_items * kGsUMax][KS]
+  const int* et_row = nullptr;     // [slots of csc_ent] item slot * kGsUMax + chunk of the entry
+  const float* counts = nullptr;   // [nnz]
+};
 void launch_gs_suff64(const int* word_ptr, const int* csc_ent, const int* order, int n_heavy, int n_medium,
                       int n_light, const double* cphi, double* cw, double* part, const double* lik,
                       const double* ass, int lo, int hi, int KS, const double* gate, hipStream_t s,
-                      const double* cw_base = nullptr);   // cw[w] = cw_base[w] + sum (nullable)
+                      const double* cw_base = nullptr,   // cw[w] = cw_base[w] + sum (nullable)
+                      const SuffRecompArgs& rc = SuffRecompArgs());
 // Staged rows refilled by the M-step launch itself (trailing workgroups): the next E-step's staged
 // copies of the longest documents' beta rows (launch_gs_stage's layout) computed straight from cw and
 // class_total, so no separate stage launch (and its inter-kernel gap) sits between the M-step and the

@@ -2224,6 +2224,10 @@ __global__ __launch_bounds__(wteam_threads(NW)) void gs_wteam(GSArgs a) {
 // EP (early prefetch): rounds u < EP of the next chunk's rows are gathered
 // into bc[u] as soon as the axpy of round u has consumed them -- before the topic sums and the
 // arrival -- so the address unit works beside the reduction; the other rounds after the arrival.
+// Outside the sweeps (profiles/defer_final.md), both optional and bitwise neutral: the chunk count sums
+// come from the plan's table (GSArgs::csum) instead of a pass over the document's counts, and the final
+// pass (every entry's c*phi row: re-reading all rows and writing as many on this one CU) is left to the
+// suff-stats pass when GSArgs::et is set -- the topic wave then copies out Et, the E each chunk used.
 // (Measured slower and removed in round 5, records in profiles/r4_tuning_log.md: the topic wave summing
 // the word waves' lane partials, 5 or 3 word waves, two early rounds, the LDS-ring loader variant.)
 template <int KS, int NW, int RMAX, int EP = 0, bool STG = false>
@@ -2237,6 +2241,9 @@ __global__ __launch_bounds__((NW + 1) * 64) void gs_wsteam(GSArgs a) {
   __shared__ double Cs[kGsUMax];        // chunk count sums
   __shared__ double sScal[NW + 1][4];   // sweep partials: lw per word wave; gamma sums (topic wave)
   __shared__ int arrive[NW];            // per word wave: chunks whose topic sums it has left in sRed
+  __shared__ int sDefer;                // a.et != nullptr, for the word waves after their sweeps: read from LDS
+                                        // so that no kernel argument more stays live in SGPRs across the chunk
+                                        // loop (the kernel is at the SGPR limit; profiles/defer_final.md)
   if (a.params[kParamDone] != 0.0) return;
   const int t = threadIdx.x;
   const int d = a.order[blockIdx.x];
@@ -2256,11 +2263,17 @@ __global__ __launch_bounds__((NW + 1) * 64) void gs_wsteam(GSArgs a) {
   const bool active = wv < nact;        // word waves holding words of a chunk (never the topic wave)
   const int* __restrict__ wrow = a.word_idx + s0;
   const float* __restrict__ crow = a.counts + s0;
-  for (int j = t; j < nch; j += NTD) Cs[j] = 0.0;
+  // chunk count sums: constants of the corpus, taken from the plan's table (a.csum, nch plain loads) when
+  // there is one; else summed here, one exposed global load and one LDS atomic per word and thread
+  const double* __restrict__ cs = a.csum != nullptr ? a.csum + (size_t)blockIdx.x * kGsUMax : nullptr;
+  for (int j = t; j < nch; j += NTD) Cs[j] = cs != nullptr ? cs[j] : 0.0;
   if (t < NW) arrive[t] = 0;
+  if (t == NTD - 1) sDefer = a.et != nullptr;
   lds_barrier();
-  for (int p = t; p < n; p += NTD) atomicAdd(&Cs[p / W], (double)crow[p]);   // integer counts: exact
-  lds_barrier();
+  if (cs == nullptr) {   // workgroup-uniform
+    for (int p = t; p < n; p += NTD) atomicAdd(&Cs[p / W], (double)crow[p]);   // integer counts: exact
+    lds_barrier();
+  }
   double total = 0.0;
   for (int j = 0; j < nch; ++j) total += Cs[j];
   const double g0 = alpha + total / K;
@@ -2373,6 +2386,13 @@ __global__ __launch_bounds__((NW + 1) * 64) void gs_wsteam(GSArgs a) {
       a.lik[d] = L;
       a.alpha_ss[d] = ps - K * psi_only(GS);
       a.iters[d] = it;
+    }
+    // deferred final pass (a.et): the E each chunk used in the final sweep -- this wave's own Et -- leaves for
+    // the suff-stats pass, which recomputes this document's c*phi rows on the whole GPU (gs_suff64 RECOMP)
+    // instead of this one CU writing and that pass re-reading them
+    if (a.et != nullptr && k < KS) {
+      double* __restrict__ eo = a.et + (size_t)blockIdx.x * kGsUMax * KS;
+      for (int j = 0; j < nch; ++j) eo[j * KS + k] = Et[j][k];
     }
     return;
   }
@@ -2525,6 +2545,7 @@ __global__ __launch_bounds__((NW + 1) * 64) void gs_wsteam(GSArgs a) {
   }
   if (timer)
     for (int i = 0; i < 8; ++i) a.dbg[i] = ph[i];
+  if (sDefer) return;   // deferred final pass (workgroup-uniform): the topic wave has left Et in a.et
   // final pass: c_n phi_nk = E_jk b_nk r_n with the final sweep's chunk E (same P as the sweep)
   if (!active) return;
   for (int j = 0; j < nch; ++j) {
@@ -2533,23 +2554,12 @@ __global__ __launch_bounds__((NW + 1) * 64) void gs_wsteam(GSArgs a) {
 #pragma unroll
     for (int kk = 0; kk < KS; ++kk) E[kk] = Et[j][kk];
     for (int p = n0 + t; p < n1; p += NS) {
-      double b[KS];
+      double b[KS], v[KS];
       load_row(row_of(p), b);
-      double p0 = 0.0, p1 = 0.0, p2 = 0.0, p3 = 0.0;
-#pragma unroll
-      for (int kk = 0; kk < KS; kk += 4) {
-        p0 = fma(E[kk], b[kk], p0);
-        if (kk + 1 < KS) p1 = fma(E[kk + 1], b[kk + 1], p1);
-        if (kk + 2 < KS) p2 = fma(E[kk + 2], b[kk + 2], p2);
-        if (kk + 3 < KS) p3 = fma(E[kk + 3], b[kk + 3], p3);
-      }
-      const double r = (double)crow[p] * drcp((p0 + p1) + (p2 + p3));
+      cphi_row<KS, 1>(E, b, (double)crow[p], v);
       dvec2* row = reinterpret_cast<dvec2*>(a.cphi + (size_t)(s0 + p) * KS);
 #pragma unroll
-      for (int kk = 0; kk < KS / 2; ++kk) {
-        const dvec2 v = {E[2 * kk] * b[2 * kk] * r, E[2 * kk + 1] * b[2 * kk + 1] * r};
-        __builtin_nontemporal_store(v, &row[kk]);
-      }
+      for (int kk = 0; kk < KS / 2; ++kk) __builtin_nontemporal_store(dvec2{v[2 * kk], v[2 * kk + 1]}, &row[kk]);
     }
   }
 }
@@ -2557,14 +2567,19 @@ __global__ __launch_bounds__((NW + 1) * 64) void gs_wsteam(GSArgs a) {
 // ------------------------------------------------------------ suff stats ----
 // One word per workgroup (heavy) / wave (medium) / 16 lanes (light); a CSC entry's
 // row is read by TG lanes (KPL topics each), S = G / TG entries in flight per group.
-template <int KS>
+// RECOMP (KS <= 32, the late pass of a deferred longest-document bucket, em.py): slot s's row is not loaded from
+// cphi but computed -- the word's beta row (once per word: all of its entries share it), the chunk's final-sweep
+// E at rc.et[rc.et_row[s]] (left by gs_wsteam, L2-resident: U x KS doubles per document) and the entry's
+// count, through the final pass's own cphi_row: the TG = 4 lanes of an entry hold topics q + 4 i, lane q the
+// chain p_q.  The rows, their order of summation and hence class_word are bitwise the materialised path's.
+template <int KS, bool RECOMP = false>
 __global__ __launch_bounds__(256) void gs_suff64(const int* __restrict__ word_ptr, const int* __restrict__ csc_ent,
                                                  const int* __restrict__ order, int n_heavy, int n_medium,
                                                  int n_light, const double* __restrict__ cphi,
                                                  double* cw, double* __restrict__ part,
                                                  const double* __restrict__ lik, const double* __restrict__ ass,
                                                  int lo, int hi, const double* gate,
-                                                 const double* cw_base) {
+                                                 const double* cw_base, SuffRecompArgs rc) {
   // one topic per lane: the paired 16-byte loads of the team kernels measured slower here (K = 100 early
   // pass 2.06 -> 2.62 ms, r5v); the c.phi pad row (em.py) is kept so PAIR stays a one-line switch
   constexpr int TG = tg_of(KS), NSLOT = 256 / TG;
@@ -2612,10 +2627,25 @@ __global__ __launch_bounds__(256) void gs_suff64(const int* __restrict__ word_pt
     const int w = order[base + item];
     int e = word_ptr[w] + sidx;
     const int end = word_ptr[w + 1];
+    double bw[KPL];
+    if constexpr (RECOMP) {
+      static_assert(!RECOMP || (TG == 4 && !PAIR && KS % 4 == 0), "recomputed rows: a quad of lanes per entry");
+      load_row<KS, KPL, TG, PAIR>(rc.beta, w, q, bw);
+    }
+    // the row of CSC slot x (the 4 lanes of an entry share x, so the quad is active as a whole)
+    auto entry = [&](int x, double (&v)[KPL]) {
+      if constexpr (RECOMP) {
+        double Ev[KPL];
+        load_row<KS, KPL, TG, PAIR>(rc.et, rc.et_row[x], q, Ev);
+        cphi_row<KPL, 4>(Ev, bw, (double)rc.counts[csc_ent[x]], v);
+      } else {
+        load_row<KS, KPL, TG, PAIR>(cphi, csc_ent[x], q, v);
+      }
+    };
     for (; e + 3 * S < end; e += 4 * S) {
       double v[4][KPL];
 #pragma unroll
-      for (int u = 0; u < 4; ++u) load_row<KS, KPL, TG, PAIR>(cphi, csc_ent[e + u * S], q, v[u]);
+      for (int u = 0; u < 4; ++u) entry(e + u * S, v[u]);
 #pragma unroll
       for (int u = 0; u < 4; ++u)
 #pragma unroll
@@ -2623,7 +2653,7 @@ __global__ __launch_bounds__(256) void gs_suff64(const int* __restrict__ word_pt
     }
     for (; e < end; e += S) {
       double v[KPL];
-      load_row<KS, KPL, TG, PAIR>(cphi, csc_ent[e], q, v);
+      entry(e, v);
 #pragma unroll
       for (int i = 0; i < KPL; ++i) acc[i] += v[i];
     }
@@ -3020,14 +3050,24 @@ int suff_fused_blocks(int n_heavy, int n_medium, int n_light) {
 void launch_gs_suff64(const int* word_ptr, const int* csc_ent, const int* order, int n_heavy, int n_medium,
                       int n_light, const double* cphi, double* cw, double* part, const double* lik,
                       const double* ass, int lo, int hi, int KS, const double* gate, hipStream_t s,
-                      const double* cw_base) {
+                      const double* cw_base, const SuffRecompArgs& rc) {
   const int nb = suff_fused_blocks(n_heavy, n_medium, n_light);
   if (nb <= 0) return;
+  const bool recomp = rc.et != nullptr;
+  if (recomp && (KS > 32 || !rc.beta || !rc.et_row || !rc.counts))
+    throw std::runtime_error("gs_suff64: recomputed rows need KS <= 32 and beta, et, et_row, counts");
   switch (KS) {
-#define ONI_KS(X)                                                                                        \
-  case X:                                                                                                \
-    hipLaunchKernelGGL((gs::gs_suff64<X>), dim3(nb), dim3(256), 0, s, word_ptr, csc_ent, order, n_heavy, \
-                       n_medium, n_light, cphi, cw, part, lik, ass, lo, hi, gate, cw_base);              \
+#define ONI_KS(X)                                                                                             \
+  case X:                                                                                                     \
+    if constexpr (X <= 32) {                                                                                  \
+      if (recomp) {                                                                                           \
+        hipLaunchKernelGGL((gs::gs_suff64<X, true>), dim3(nb), dim3(256), 0, s, word_ptr, csc_ent, order,     \
+                           n_heavy, n_medium, n_light, cphi, cw, part, lik, ass, lo, hi, gate, cw_base, rc);  \
+        break;                                                                                                \
+      }                                                                                                       \
+    }                                                                                                         \
+    hipLaunchKernelGGL((gs::gs_suff64<X>), dim3(nb), dim3(256), 0, s, word_ptr, csc_ent, order, n_heavy,      \
+                       n_medium, n_light, cphi, cw, part, lik, ass, lo, hi, gate, cw_base, rc);               \
     break;
     ONI_FOR_EACH_KS(ONI_KS)
 #undef ONI_KS

@@ -188,7 +188,7 @@ class LDAEngine:
                  streams: int = 4, local_shard: bool = False, split_docs: bool = True,
                  split_min: Optional[int] = 4096, use_graph: bool = True, precision: str = "fp64",
                  emulate_shards: int = 0, doc_offset: int = 0, cphi_gb: Optional[float] = None,
-                 suff_split: str = "auto", xsplit: Optional[dict] = None):
+                 suff_split: str = "auto", xsplit: Optional[dict] = None, defer_final: bool = True):
         """precision: "fp64" (the only engine: lda-c's double arithmetic; the hip backend runs the block
         Gauss-Seidel schedule of lda_gs64.hip).
         emulate_shards (torch backend, one process): reduce the sufficient statistics as the N
@@ -201,8 +201,13 @@ class LDAEngine:
         its share of the sufficient statistics (``_cphi_windows``).  None: ONI_CPHI_GB, else windows
         only when the rows would take more than 35 % of the GPU's memory.
         suff_split (fp64 hip engine): "auto" -- the longest-document bucket's entries reduced after it, the
-        others while it still runs (``_build_suff_split``) when that overlaps anything; "off"; "force"."""
+        others while it still runs (``_build_suff_split``) when that overlaps anything; "off"; "force".
+        defer_final (fp64 hip engine, K <= 32, U <= 32): with the early / late split, the longest-document
+        launch leaves its chunks' final-sweep E instead of writing its c.phi rows, and the late pass
+        recomputes them (bitwise the same rows, computed by the whole GPU instead of the one CU every EM
+        iteration waits for); False: the launch writes them itself (A/B runs)."""
         self.cphi_gb = cphi_gb
+        self.defer_final = bool(defer_final)
         if suff_split not in ("auto", "off", "force"):
             raise ValueError(f"suff_split must be auto | off | force, got {suff_split!r}")
         self.suff_split = suff_split
@@ -415,6 +420,7 @@ class LDAEngine:
         # one zero pad row past the vocabulary: gs_smallw's constant-offset row loads may read past row V - 1
         self.beta = torch.zeros(V + 1, KS, dtype=f64, device=dev)[:V]
         self._stages = self._build_stages(corpus, KS)
+        self._csums = self._build_chunk_sums(corpus, KS)
         self.cw = torch.zeros(V, KS, dtype=f64, device=dev)
         self.gamma = torch.zeros(D, KS, dtype=f64, device=dev)
         # one pad row past the last entry: the suff-stats kernel's paired row loads (KS > 32) may read into it
@@ -461,6 +467,14 @@ class LDAEngine:
         if isinstance(gp.split, H.GSSplitPlan):
             gp.split.chunk_sums(corpus.doc_ptr, corpus.counts)
 
+    def _order_host(self, order) -> np.ndarray:
+        """Host copy of a plan's order tensor, read back once (every read-back is a device synchronise
+        inside the engine's setup time)."""
+        memo = self.__dict__.setdefault("_order_np", {})
+        if id(order) not in memo:
+            memo[id(order)] = (order, order.cpu().numpy())     # the tensor is kept: ids are not reused
+        return memo[id(order)][1]
+
     def _build_stages(self, corpus: Corpus, KS: int) -> dict:
         """Staged beta rows (ops/hip.py GSStage) of every kGsTeam8 launch at KS <= 32, keyed by the id of
         the launch's order tensor.  ONI_GS_STAGE = the budget in GB (default 4; 0 turns them off): a plan
@@ -476,15 +490,27 @@ class LDAEngine:
             for var, order in gp.plan:
                 if var != H.GS_TEAM8:
                     continue
-                o = order.cpu().numpy()
-                o = o[o >= 0]
+                oh = self._order_host(order)
+                o = oh[oh >= 0]
                 # GSStage pads every document to whole 64-row tiles
                 need = int((-(-(corpus.doc_ptr[o + 1] - corpus.doc_ptr[o]) // 64)).sum()) * 64 * KS * 8
                 if need > cap:
                     continue
                 cap -= need
-                out[id(order)] = H.GSStage(order, corpus.doc_ptr, KS, self.device)
+                out[id(order)] = H.GSStage(oh, corpus.doc_ptr, KS, self.device)
         return out
+
+    def _build_chunk_sums(self, corpus: Corpus, KS: int) -> dict:
+        """Chunk count sums (ops/hip.py gs_chunk_sums) of every kGsTeam8 launch that runs the word-wave
+        kernel (KS <= 32, U <= 32), keyed by the id of the launch's order tensor: constants of the corpus,
+        built once per plan instead of summed by every E-step's longest-document workgroups."""
+        from ...ops import hip as H
+        if KS > 32 or self._U > H.GS_LDS_UMAX:
+            return {}
+        plans = [self.gs_plan] if self._cwin is None else [w["gp"] for w in self._cwin]
+        return {id(order): H.gs_chunk_sums(self._order_host(order), corpus.doc_ptr, corpus.counts, self._U,
+                                           self.device)
+                for gp in plans for var, order in gp.plan if var == H.GS_TEAM8}
 
     def _cphi_windows(self, corpus: Corpus, KS: int):
         """Contiguous document windows [d0, d1) of <= the c.phi budget's rows each (nnz-balanced, a
@@ -554,7 +580,7 @@ class LDAEngine:
         if key == "split":
             late = np.asarray(sorted(gp.split.segments), np.int64)
         else:
-            o = gp.plan[key][1].cpu().numpy()
+            o = self._order_host(gp.plan[key][1])
             late = o[o >= 0].astype(np.int64)
         force = self.suff_split == "force"
         if late.size == 0 or (not force and dc.doc_len[late].sum() > 0.6 * max(1, int(dc.doc_len.sum()))):
@@ -567,8 +593,17 @@ class LDAEngine:
         need = max(planE.n_blocks, planL.n_blocks, 1)
         if self._suff_part.shape[0] < need:
             self._suff_part = torch.zeros(need, self._suff_part.shape[1], dtype=torch.float64, device=dev)
-        return dict(wpE=wpE, ceE=ceE, planE=planE, wpL=wpL, ceL=ceL, planL=planL,
-                    cw_early=torch.zeros_like(self.cw), late_docs=int(late.size))
+        out = dict(wpE=wpE, ceE=ceE, planE=planE, wpL=wpL, ceL=ceL, planL=planL,
+                   cw_early=torch.zeros_like(self.cw), late_docs=int(late.size))
+        # deferred final pass: the late bucket is the word-wave kernel's launch (kGsTeam8, U <= 32); it leaves
+        # its chunks' E in et, and the late pass recomputes the rows of its entries (et_row: the E row of
+        # every late CSC slot, fixed by the plan)
+        if self.defer_final and key != "split" and gp.plan[key][0] == H.GS_TEAM8 and self._U <= H.GS_LDS_UMAX:
+            order = gp.plan[key][1]
+            out["et_order"] = id(order)
+            out["et"] = torch.zeros(order.numel() * H.GS_LDS_UMAX * self.KS, dtype=torch.float64, device=dev)
+            out["et_row"] = H.gs_et_rows(ceL, self._order_host(order), self.corpus.doc_ptr, self._U)
+        return out
 
     def _stream_slots(self, gp, late: bool) -> list:
         """Stream of every work item ([split] + gp.plan) as _launch_buckets dispatches them: 0 = the current
@@ -706,7 +741,9 @@ class LDAEngine:
         # and this E-step uses the rows the previous M-step (or the batch's opening refill) left
         fused = newton_key is not None and phase == "all" and bool(self._fused_stages(gp))
         grp = ss if (ss is not None and ss.get("mode") == "groups" and phase == "all") else None
-        used, late_s = self._launch_buckets(gp, ss is not None, fused_stage=fused, groups=grp)
+        # deferred final pass of the late bucket (_build_suff_split): only here, where the late pass follows
+        defer = ss if (ss is not None and grp is None and ss.get("et") is not None) else None
+        used, late_s = self._launch_buckets(gp, ss is not None, fused_stage=fused, groups=grp, defer=defer)
         if phase == "estep":             # the document kernels only (final inference pass)
             return
         scal = (self.lik, self.ass, 0, self.lik.numel())
@@ -721,7 +758,8 @@ class LDAEngine:
             H.gs_suff64(ss["wpE"], ss["ceE"], ss["planE"], self.cphi, ss["cw_early"], self._suff_part, gate=gate)
             main.wait_event(self._ev_join[used.index(late_s)])
             H.gs_suff64(ss["wpL"], ss["ceL"], ss["planL"], self.cphi, self._cw_local, self._suff_part, gate=gate,
-                        scalars=scal, base=ss["cw_early"])
+                        scalars=scal, base=ss["cw_early"],
+                        recomp=None if defer is None else (self.beta, ss["et"], ss["et_row"], dc.counts))
             H.colsum_partials(self._suff_part, ss["planL"].n_blocks, self._red_local, gate=gate)
             self._finish_suff64(newton_key, stages=self._fused_stages(gp) if fused else ())
             return
@@ -752,11 +790,13 @@ class LDAEngine:
         for st in self._fused_stages(self.gs_plan):
             H.gs_stage(self.beta, self.dc.word_idx, st, gate=self._gate)
 
-    def _launch_buckets(self, gp, late: bool = False, win=None, fused_stage: bool = False, groups=None):
+    def _launch_buckets(self, gp, late: bool = False, win=None, fused_stage: bool = False, groups=None,
+                        defer=None):
         """The document kernels of GSPlan ``gp`` on 4 streams, joined back into the current stream.
         late: work[0] (the longest-document bucket) stays un-joined on streams[1], returned as late_s,
         for the early / late suff-stats; win: one of the c.phi windows (``_cphi_windows``) -- the document
-        kernels write its entries into the first rows of the shared buffer."""
+        kernels write its entries into the first rows of the shared buffer; defer: the suff split whose late
+        bucket leaves its chunk E in defer["et"] instead of writing its c.phi rows."""
         from ...ops import hip as H
         dc, prm = self.dc, self._params
         main = torch.cuda.current_stream(self.device)
@@ -800,8 +840,10 @@ class LDAEngine:
                                cphi, self.lik, self.ass, self.iters, batch, ent_base=ent_base)
                 else:
                     st = self._stages.get(id(order))
+                    et = defer["et"] if (defer is not None and defer["et_order"] == id(order)) else None
                     H.gs_estep(dc.doc_ptr, dc.word_idx, dc.counts, order, self.beta, self.K, self._U, prm,
-                               self.gamma, cphi, self.lik, self.ass, self.iters, var, ent_base=ent_base, stage=st)
+                               self.gamma, cphi, self.lik, self.ass, self.iters, var, ent_base=ent_base, stage=st,
+                               csum=self._csums.get(id(order)), et=et)
         if groups is not None:
             for g in groups["groups"]:
                 with torch.cuda.stream(streams[g["slot"]]):

@@ -415,6 +415,7 @@ def bin_columns(values, cuts):
 # chunk of ceil(n / gs_updates) words (documents of <= gs_updates words: lda-c's per-word schedule).
 GS_TINY, GS_TEAM1, GS_TEAM4, GS_TEAM8, GS_SMALL, GS_CHAIN = range(6)
 GS_SMALL_MAX = 64   # csrc/hip/lda_gs64.hip kGsSmallMax
+GS_LDS_UMAX = 32    # csrc/hip/kernels.h kGsUMax: largest U with the chunk tables in LDS (rows of csum / et)
 
 
 def gs_umax(KS: int = 0) -> int:
@@ -513,12 +514,76 @@ def _need_pad_row(t):
         raise ValueError("the table needs a pad row past its last row ([n + 1, KS] storage, view [:n])")
 
 
+def gs_chunk_sums(order, doc_ptr, counts, gs_updates: int, device):
+    """[n_items, GS_LDS_UMAX] float64: row i holds the chunk count sums of document ``order[i]`` (chunks of
+    W = ceil(n / U) words; zeros past its last chunk and for the placement gaps ``order[i] < 0``), from the
+    corpus' host ``doc_ptr`` / ``counts`` -- sums of integer counts, exact.  The longest-document kernel
+    (gs_wsteam) reads them instead of summing the counts in every E-step (``gs_estep(csum=...)``)."""
+    import numpy as np
+    U = int(gs_updates)
+    if not 1 <= U <= GS_LDS_UMAX:
+        raise ValueError(f"chunk sums: U = {U} outside 1..{GS_LDS_UMAX}")
+    o = np.asarray(order.cpu().numpy() if torch.is_tensor(order) else order, np.int64)
+    dp = np.asarray(doc_ptr, np.int64)
+    cnt = np.asarray(counts)
+    out = np.zeros((o.size, GS_LDS_UMAX), np.float64)
+    item = np.flatnonzero(o >= 0)
+    s0 = dp[o[item]]
+    n = dp[o[item] + 1] - s0
+    item, s0, n = item[n > 0], s0[n > 0], n[n > 0]
+    if item.size:
+        W = -(-n // U)
+        nch = -(-n // W)
+        # only these documents' counts, back to back (the corpus' other entries are never touched: the
+        # table is built inside the engine's setup time); a chunk then ends where the next one starts
+        own = np.concatenate([cnt[a:a + m] for a, m in zip(s0.tolist(), n.tolist())])
+        if own.dtype != np.int64:                     # int64 counts (Corpus) are summed as they are: exact, no cast
+            own = own.astype(np.float64)
+        rep = np.repeat(np.arange(item.size), nch)
+        j = np.arange(rep.size) - np.repeat(np.cumsum(nch) - nch, nch)
+        out[item[rep], j] = np.add.reduceat(own, (np.cumsum(n) - n)[rep] + j * W[rep])
+    return torch.from_numpy(out).to(device)
+
+
+def gs_et_rows(csc_ent, order, doc_ptr, gs_updates: int):
+    """int32 per slot of ``csc_ent`` (device; every entry lies in a document of ``order``): item slot *
+    GS_LDS_UMAX + the entry's chunk (position in the document // W), the row of ``gs_estep(et=...)``'s table
+    that holds the E its c.phi row is computed with.  The per-document values (a few rows) come from the
+    host ``doc_ptr``; the per-slot work is device gathers."""
+    import numpy as np
+    dev = csc_ent.device
+    o = np.asarray(order.cpu().numpy() if torch.is_tensor(order) else order, np.int64)
+    dp = np.asarray(doc_ptr, np.int64)
+    slot = np.flatnonzero(o >= 0)
+    s0 = dp[o[slot]]
+    n = dp[o[slot] + 1] - s0
+    slot, s0, n = slot[n > 0], s0[n > 0], n[n > 0]     # an empty document shares its start with the next one
+    if slot.size == 0:
+        if csc_ent.numel():
+            raise ValueError("gs_et_rows: entries but no document")
+        return torch.zeros(0, dtype=torch.int32, device=dev)
+    srt = np.argsort(s0, kind="stable")
+    slot, s0, n = slot[srt], s0[srt], n[srt]
+    W = -(-n // int(gs_updates))
+    t_s0, t_W, t_base = torch.from_numpy(np.stack([s0, W, slot * GS_LDS_UMAX])).to(dev)     # one upload
+    ent = csc_ent.long()
+    i = (torch.searchsorted(t_s0, ent, right=True) - 1).clamp_(min=0)             # the entry's document
+    # no read-back to validate (a device synchronise inside the engine's setup time): the caller's entries are
+    # those of these documents by construction (csc_subset over the same documents), and the clamp keeps any
+    # other entry's row inside its document's GS_LDS_UMAX rows
+    chunk = ((ent - t_s0[i]) // t_W[i]).clamp_(0, GS_LDS_UMAX - 1)
+    return (t_base[i] + chunk).to(torch.int32)
+
+
 def gs_estep(doc_ptr, word_idx, counts, order, beta, K, gs_updates, params, gamma, cphi, lik, alpha_ss, iters, variant,
-             dbg=None, ent_base=None, stage: Optional["GSStage"] = None):
+             dbg=None, ent_base=None, stage: Optional["GSStage"] = None, csum=None, et=None):
     """One launch of the fp64 block Gauss-Seidel E-step over the documents in ``order``.
     ``params``: the device parameter block {alpha, lgamma constant, VAR_MAX_ITER, VAR_CONVERGED, done}.
     ``ent_base``: ``cphi`` is a window starting at that corpus entry (_cphi_ptr).
-    ``stage``: the GSStage of this (kGsTeam8) launch, filled by ``gs_stage`` from the current beta."""
+    ``stage``: the GSStage of this (kGsTeam8) launch, filled by ``gs_stage`` from the current beta.
+    ``csum`` (kGsTeam8, KS <= 32, U <= 32): the launch's chunk count sums (``gs_chunk_sums``).
+    ``et`` (same launches) [n_items * 32 * KS] float64: the deferred final pass -- the kernel leaves every
+    chunk's final-sweep E there and writes no c.phi rows; ``gs_suff64(recomp=...)`` recomputes them."""
     D = doc_ptr.numel() - 1
     nnz = word_idx.numel()
     V, KS = beta.shape
@@ -546,19 +611,26 @@ def gs_estep(doc_ptr, word_idx, counts, order, beta, K, gs_updates, params, gamm
         int(variant), _stream(), 0 if dbg is None else _chk(dbg, torch.int64, "dbg", (16,), dev),
         0 if stage is None else _chk(stage.buf, torch.float64, "stage", None, dev),
         0 if stage is None else _chk(stage.stage_off, torch.int64, "stage_off", (order.numel(),), dev),
+        0 if csum is None else _chk(csum, torch.float64, "csum", (order.numel(), GS_LDS_UMAX), dev),
+        0 if et is None else _chk(et, torch.float64, "et", (order.numel() * GS_LDS_UMAX * KS,), dev),
     ]
     _need_pad_row(beta)
     if stage is not None and (variant != GS_TEAM8 or KS != stage.KS):
         raise ValueError("staged rows: kGsTeam8 launches of the stage's KS only")
+    if (csum is not None or et is not None) and (variant != GS_TEAM8 or KS > 32 or int(gs_updates) > GS_LDS_UMAX):
+        raise ValueError("chunk sums / deferred final pass: kGsTeam8 launches at KS <= 32, U <= 32 only")
     if order.numel() == 0:
         return
     lib().gs_estep(*args)
 
 
-def gs_suff64(word_ptr, csc_ent, plan: "SuffPlan", cphi, cw, part, gate=None, scalars=None, base=None):
+def gs_suff64(word_ptr, csc_ent, plan: "SuffPlan", cphi, cw, part, gate=None, scalars=None, base=None, recomp=None):
     """class_word[w] = sum of the cphi rows of w's corpus entries (CSC order, fp64, no atomics) + per-workgroup
     partial rows part[b] = {lik slice, alpha_ss slice, column sums} for ``colsum_partials``.
-    ``base`` [V, KS] (optional): added to each written row first (cw[w] = base[w] + sum)."""
+    ``base`` [V, KS] (optional): added to each written row first (cw[w] = base[w] + sum).
+    ``recomp`` = (beta, et, et_row, counts) (KS <= 32): the rows are not read from ``cphi`` but recomputed,
+    bitwise as the deferred longest-document launch (``gs_estep(et=...)``) would have written them, from the
+    word's beta row, the chunk E at row ``et_row[s]`` (``gs_et_rows``) of ``et`` and the entry's count."""
     V, KS = cw.shape
     nnz = cphi.shape[0]            # csc_ent may be a subset of the corpus entries (csc_subset)
     dev = cw.device
@@ -578,12 +650,21 @@ def gs_suff64(word_ptr, csc_ent, plan: "SuffPlan", cphi, cw, part, gate=None, sc
     else:
         D = scalars[0].numel()
         lik, ass, lo, hi = _scalar_slice(scalars, D, dev)
+    rc = (0, 0, 0, 0)
+    if recomp is not None:
+        r_beta, r_et, r_row, r_cnt = recomp
+        if KS > 32 or r_et.numel() % (GS_LDS_UMAX * KS):
+            raise ValueError("recomputed rows: KS <= 32 and et of [n_items * 32 * KS]")
+        # et_row / csc_ent values are bounds-checked where they are built (gs_et_rows, csc_subset)
+        rc = (_chk(r_beta, torch.float64, "beta", (V, KS), dev), _chk(r_et, torch.float64, "et", None, dev),
+              _chk(r_row, torch.int32, "et_row", (csc_ent.numel(),), dev),
+              _chk(r_cnt, torch.float32, "counts", (nnz,), dev))
     lib().gs_suff64(
         _chk(word_ptr, torch.int32, "word_ptr", (V + 1,), dev), _chk(csc_ent, torch.int32, "csc_ent", None, dev),
         _chk(plan.order, torch.int32, "order", (plan.order.numel(),), dev), plan.n_heavy, plan.n_medium, plan.n_light,
         _chk(cphi, torch.float64, "cphi", (nnz, KS), dev), _chk(cw, torch.float64, "cw", (V, KS), dev),
         _chk(part, torch.float64, "part", None, dev), lik, ass, lo, hi, int(KS), _gate_ptr(gate, dev), _stream(),
-        0 if base is None else _chk(base, torch.float64, "base", (V, KS), dev))
+        0 if base is None else _chk(base, torch.float64, "base", (V, KS), dev), *rc)
 
 
 def csc_subset(word_ptr, csc_ent, csc_doc, doc_mask):

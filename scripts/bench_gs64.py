@@ -50,6 +50,10 @@ def main():
     ap.add_argument("--vocab", type=int, default=4_536_586, help="--long: vocabulary (config 5's month)")
     ap.add_argument("--sweeps", type=int, default=0, help="timed launches run exactly this many sweeps (no "
                                                            "convergence test), e.g. 20: a long document's real count")
+    ap.add_argument("--team8", default="defer", choices=["plain", "csum", "defer"],
+                    help="the team8 (gs_wsteam) launch: plain = it sums the chunk counts and writes its c.phi rows; "
+                         "csum = chunk count sums from the plan's table; defer = csum + the final pass left to the "
+                         "suff-stats pass (the engine's default)")
     a = ap.parse_args()
     from oni_ml_amd.models.lda.em import LDAEngine
     from oni_ml_amd.models.lda.settings import LDASettings
@@ -87,8 +91,18 @@ def main():
         st = eng._stages.get(id(order))   # team8's staged rows (ops/hip.py GSStage): refill + launch
         if st is not None:
             H.gs_stage(eng.beta, dc.word_idx, st)
+        cs = et = None
+        if var == H.GS_TEAM8 and a.team8 != "plain" and eng.KS <= 32 and eng._U <= H.GS_LDS_UMAX:
+            if id(order) not in eng._csums:     # --first: a shortened launch
+                eng._csums[id(order)] = H.gs_chunk_sums(order, c.doc_ptr, c.counts, eng._U, order.device)
+            cs = eng._csums[id(order)]
+            if a.team8 == "defer":
+                et = et_buf.setdefault(id(order), torch.zeros(order.numel() * H.GS_LDS_UMAX * eng.KS,
+                                                              dtype=torch.float64, device=order.device))
         H.gs_estep(dc.doc_ptr, dc.word_idx, dc.counts, order, eng.beta, eng.K, eng._U, eng._params, eng.gamma,
-                   eng.cphi, eng.lik, eng.ass, eng.iters, var, dbg=dbg, stage=st)
+                   eng.cphi, eng.lik, eng.ass, eng.iters, var, dbg=dbg, stage=st, csum=cs, et=et)
+
+    et_buf = {}
 
     spl = eng.gs_plan.split
     if spl is not None and (not a.only or a.only == "split"):
@@ -177,6 +191,13 @@ def main():
         sp = eng.suff_plan
         out["suff_ms"] = round(timed(lambda: H.gs_suff64(dc.word_ptr, dc.csc_ent, sp, eng.cphi, eng.cw,
                                                          eng._suff_part, scalars=(eng.lik, eng.ass, 0, eng.D))), 4)
+        ss = eng._suff_split
+        if ss is not None and ss.get("et") is not None:
+            # the late pass (the longest-document bucket's entries): rows read from c.phi | recomputed
+            late = lambda rc: H.gs_suff64(ss["wpL"], ss["ceL"], ss["planL"], eng.cphi, eng._cw_local, eng._suff_part,
+                                          scalars=(eng.lik, eng.ass, 0, eng.D), base=ss["cw_early"], recomp=rc)
+            out["suff_late_ms"] = round(timed(lambda: late(None)), 4)
+            out["suff_late_recomp_ms"] = round(timed(lambda: late((eng.beta, ss["et"], ss["et_row"], dc.counts))), 4)
         out["estep_graph_ms"] = round(timed(lambda: eng._launch_estep()), 4)
         print(json.dumps({k: v for k, v in out.items() if k != "buckets"}), flush=True)
 
