@@ -1,6 +1,6 @@
 // fp64 math and wave-reduction helpers shared by the block Gauss-Seidel E-step kernels
-// (lda_gs64.hip: the one-workgroup document kernels; experimental/lda_xsplit.hip: one document over the CUs of
-// an XCD).  lda-c's arithmetic in short dependency chains for gfx950.
+// (gs_short.hip, gs_team.hip, gs_wteam.hip, gs_split.hip) and the suff-stats pass (lda_gs64.hip).
+// lda-c's arithmetic in short dependency chains for gfx950.
 #pragma once
 #include "common.h"
 #include "kernels.h"

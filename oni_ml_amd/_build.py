@@ -155,28 +155,6 @@ def build_hip(verbose=False, jobs=8) -> Path:
     return out
 
 
-def build_hip_exp(verbose=False, jobs=8) -> Path:
-    """csrc/hip/experimental/ (E-step variants measured not faster, for their tests and benchmarks)
-    into _onihip_exp: a module of its own, so the production code object and ml_ops never carry them."""
-    out = LIB / ("_onihip_exp" + _ext_suffix())
-    exp = CSRC / "hip" / "experimental"
-    hdrs = sorted((CSRC / "hip").glob("*.h")) + sorted(exp.glob("*.h"))
-    srcs = sorted(exp.glob("*.hip"))
-    bind = exp / "bind_exp.cpp"
-    flags = hip_flags()
-
-    def one(src):
-        o = OBJ / "hip_exp" / (src.stem + ".o")
-        extra = [f"-I{_pybind_inc()}", f"-I{_py_inc()}"] if src == bind else []
-        return _compile(src, o, [HIPCC], flags + extra, hdrs, verbose)
-
-    with ThreadPoolExecutor(max_workers=jobs) as ex:
-        objs = list(ex.map(one, srcs + [bind]))
-    link = [HIPCC, "-shared", f"--offload-arch={ARCH}", "-fPIC", "-o", str(out)] + [str(o) for o in objs]
-    _link(out, objs, link, verbose)
-    return out
-
-
 def build_native(verbose=False, jobs=8) -> Path:
     """Compile csrc/native/*.cpp (host runtime) into _oninative + the `lda` CLI binary."""
     cxx = os.environ.get("CXX", "g++")
@@ -229,9 +207,7 @@ def build_sanitized(kind: str = "thread", verbose=False) -> Path:
     return exe
 
 
-def build_all(verbose=False, hip=True, native=True, experimental=False):
-    """experimental: also build csrc/hip/experimental/ (only on request: ``python -m oni_ml_amd._build exp``;
-    ml_ops never loads it, and its tests skip without it)."""
+def build_all(verbose=False, hip=True, native=True):
     with _lock:
         RECORD.clear()
         outs = []
@@ -243,12 +219,6 @@ def build_all(verbose=False, hip=True, native=True, experimental=False):
             if not Path(HIPCC).exists():
                 raise RuntimeError(f"hipcc not found at {HIPCC}")
             outs.append(build_hip(verbose))
-            if experimental:
-                outs.append(build_hip_exp(verbose))
-            else:
-                # a stale experimental module would travel with the tree and be mapped by its tests
-                for p in LIB.glob("_onihip_exp*"):
-                    p.unlink()
         return outs
 
 
@@ -263,4 +233,4 @@ if __name__ == "__main__":
     v = "-v" in sys.argv
     if "clean" in sys.argv:
         clean()
-    print(build_all(verbose=v, experimental="exp" in sys.argv))
+    print(build_all(verbose=v))

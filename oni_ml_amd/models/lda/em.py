@@ -8,7 +8,7 @@ while (conv < 0 or conv > EM_CONV or i <= 2) and i <= EM_MAX_ITER.
 MI355X design:
 * the corpus (CSR + CSC) and the model (word-major beta, fp64 like lda-c) stay resident in
   HBM for the whole run; one EM iteration = length-bucketed fp64 block Gauss-Seidel E-step
-  kernels (csrc/hip/lda_gs64.hip, on 4 HIP streams so the long-document buckets overlap
+  kernels (csrc/hip/gs_*.hip behind lda_gs64.hip's dispatch, on 4 HIP streams so the long-document buckets overlap
   the short ones) -> deterministic CSC sufficient statistics -> (RCCL sparse row exchange
   or all-reduce when data-parallel) -> M-step + alpha Newton + the EM convergence test, all
   on the device and replayed as hipGraphs: the host reads the per-iteration history back once
@@ -188,9 +188,9 @@ class LDAEngine:
                  streams: int = 4, local_shard: bool = False, split_docs: bool = True,
                  split_min: Optional[int] = 4096, use_graph: bool = True, precision: str = "fp64",
                  emulate_shards: int = 0, doc_offset: int = 0, cphi_gb: Optional[float] = None,
-                 suff_split: str = "auto", xsplit: Optional[dict] = None, defer_final: bool = True):
+                 suff_split: str = "auto", defer_final: bool = True):
         """precision: "fp64" (the only engine: lda-c's double arithmetic; the hip backend runs the block
-        Gauss-Seidel schedule of lda_gs64.hip).
+        Gauss-Seidel schedule of lda_gs64.hip and the gs_*.hip kernel families).
         emulate_shards (torch backend, one process): reduce the sufficient statistics as the N
         document shards of ``dist.engine_bounds`` summed in shard order -- bitwise the N-rank run under
         ONI_DIST_DETERMINISTIC=1 (parallel/dist.py).
@@ -212,7 +212,6 @@ class LDAEngine:
             raise ValueError(f"suff_split must be auto | off | force, got {suff_split!r}")
         self.suff_split = suff_split
         self.n_streams = max(2, int(streams))     # the E-step buckets' streams, the current one included
-        self.xsplit = xsplit          # experimental XCD-split plan of the longest documents (ops/hip.py GSPlan)
         # the fused EM iteration's M-step launch refills the next E-step's staged rows (one rank); False: a
         # gs_stage launch before every E-step (tests/test_gs64.py pins the two bitwise equal)
         self.stage_fuse = True
@@ -408,7 +407,7 @@ class LDAEngine:
         f64 = torch.float64
         self._cwin = self._cphi_windows(corpus, KS)
         if self._cwin is None:
-            self.gs_plan = H.GSPlan(self.dc.doc_len, KS, self._U, dev, xsplit=self.xsplit)
+            self.gs_plan = H.GSPlan(self.dc.doc_len, KS, self._U, dev)
             self._split_sums(self.gs_plan, corpus)
             rows = nnz
         else:
@@ -835,9 +834,8 @@ class LDAEngine:
             with torch.cuda.stream(s):
                 if var == "split":
                     for batch in order:
-                        launch = H.gs_xsplit if batch.get("x") else H.gs_split
-                        launch(dc.doc_ptr, dc.word_idx, dc.counts, self.beta, self.K, self._U, prm, self.gamma,
-                               cphi, self.lik, self.ass, self.iters, batch, ent_base=ent_base)
+                        H.gs_split(dc.doc_ptr, dc.word_idx, dc.counts, self.beta, self.K, self._U, prm, self.gamma,
+                                   cphi, self.lik, self.ass, self.iters, batch, ent_base=ent_base)
                 else:
                     st = self._stages.get(id(order))
                     et = defer["et"] if (defer is not None and defer["et_order"] == id(order)) else None

@@ -50,29 +50,6 @@ def lib():
     return _LIB
 
 
-_EXP = None
-
-
-def exp_lib():
-    """The experimental kernels' module (`_onihip_exp`: variants measured not faster, loaded only when a
-    caller asks for one -- never by ml_ops); raises loudly if it is missing."""
-    global _EXP
-    if _EXP is None:
-        lib()
-        try:
-            _EXP = importlib.import_module("_onihip_exp")
-        except Exception as e:  # pragma: no cover - depends on build state
-            raise RuntimeError(f"oni_ml_amd experimental HIP extension (_onihip_exp) failed to load: {e!r}. "
-                               "It is built only on request: `python -m oni_ml_amd._build exp`.") from e
-    return _EXP
-
-
-def exp_available() -> bool:
-    """Whether the opt-in experimental module was built (its tests skip otherwise)."""
-    import glob
-    return bool(glob.glob(os.path.join(os.path.dirname(os.path.dirname(__file__)), "_lib", "_onihip_exp*.so")))
-
-
 def compiled_ks():
     return list(lib().compiled_ks())
 
@@ -411,10 +388,10 @@ def bin_columns(values, cuts):
 
 
 # ------------------------------------------------------- fp64 block Gauss-Seidel ---
-# lda-c-faithful E-step (csrc/hip/lda_gs64.hip): double everywhere, gamma refreshed after every
+# lda-c-faithful E-step (csrc/hip/lda_gs64.hip, gs_*.hip): double everywhere, gamma refreshed after every
 # chunk of ceil(n / gs_updates) words (documents of <= gs_updates words: lda-c's per-word schedule).
 GS_TINY, GS_TEAM1, GS_TEAM4, GS_TEAM8, GS_SMALL, GS_CHAIN = range(6)
-GS_SMALL_MAX = 64   # csrc/hip/lda_gs64.hip kGsSmallMax
+GS_SMALL_MAX = 64   # csrc/hip/gs_short.hip kGsSmallMax
 GS_LDS_UMAX = 32    # csrc/hip/kernels.h kGsUMax: largest U with the chunk tables in LDS (rows of csum / et)
 
 
@@ -799,7 +776,7 @@ def gs_split_launch_cap(KS: int) -> int:
     return cap
 
 
-SPLIT_MAX_SEG = 128        # csrc/hip/lda_gs64.hip kSplitMaxSeg2 (segments per document)
+SPLIT_MAX_SEG = 128        # csrc/hip/gs_split.hip kSplitMaxSeg2 (segments per document)
 SPLIT_MAX_SEG_GATHER = 16  # kSplitMaxSeg: up to here one batched gather per chunk, above it the two-phase exchange
 
 
@@ -1049,109 +1026,6 @@ def _split_tab(batch, nb, U, KS, dev, doc_ptr):
     return 0, 0
 
 
-def gs_xsplit_rows(KS: int) -> int:
-    """LDS row capacity of one gs_xsplit member (its words over every chunk of a sweep), 0: no kernel."""
-    return int(exp_lib().gs_xsplit_rows(int(KS)))
-
-
-class GSXSplitPlan:
-    """Documents split over the CUs of one XCD each (gs_xsplit, csrc/hip/experimental/lda_xsplit.hip, even KS <= 32;
-    measured not faster than one workgroup: profiles/r5_xcd_split.md).
-
-    The first ``limit`` documents of ``doc_ids`` (longest first) that fit are taken.  Document d of n words
-    (W = ceil(n / U) words per chunk) gets G one-wave members, each holding its
-    ceil(W / G) words of every chunk in LDS: G >= the LDS minimum, ``members`` or as
-    many as that takes, at most 32 (the CUs of an XCD).  Documents are first-fit packed into the 8 XCD
-    groups (members of group x are blocks x, x + 8, ... of a grid of 8 x max-members blocks: one XCD
-    under the observed round-robin dispatch); a document that fits no group stays with the team
-    kernels (``leftover``).  Duck-types GSSplitPlan for the engine (segments, batches, n_docs)."""
-
-    def __init__(self, doc_ids, lengths, KS: int, gs_updates: int, device, members: int = 0, groups: int = 8,
-                 proto: int = 1, limit: int = 0):
-        import numpy as np
-        self.KS, U = int(KS), int(gs_updates)
-        cap = gs_xsplit_rows(KS)
-        if cap <= 0 or not 1 <= U <= 32:
-            raise ValueError(f"gs_xsplit: no kernel for KS {KS} / U {U}")
-        members = int(members)
-        self.proto = int(proto)
-        used = [0] * 8
-        slots = [[] for _ in range(8)]          # per group: (doc, G)
-        self.segments, self.leftover = {}, []
-        for d in doc_ids:
-            if limit and len(self.segments) >= limit:
-                break
-            n = int(lengths[d])
-            W = -(-n // U)
-            nch = -(-n // W)
-            per = cap // nch                     # words of one chunk a member can hold
-            gmin = -(-W // per) if per > 0 else 10 ** 9
-            G = max(gmin, min(members, W) if members else gmin, 2)
-            x = next((x for x in range(min(groups, 8)) if used[x] + G <= 32), None)
-            if G > 32 or x is None or W < 2:
-                self.leftover.append(int(d))
-                continue
-            slots[x].append((int(d), G))
-            used[x] += G
-            self.segments[int(d)] = G
-        self.n_docs = len(self.segments)
-        gmax = max(used) if self.n_docs else 0
-        nb = 8 * gmax
-        seg_doc = np.full(nb, -1, np.int32)
-        seg_index = np.zeros(nb, np.int32)
-        seg_count = np.ones(nb, np.int32)
-        seg_base = np.zeros(nb, np.int32)
-        doc_slot = np.zeros(nb, np.int32)
-        row, slot = 0, 0
-        for x in range(8):
-            m = 0
-            for d, G in slots[x]:
-                for gi in range(G):
-                    b = x + 8 * (m + gi)
-                    seg_doc[b], seg_index[b], seg_count[b], seg_base[b], doc_slot[b] = d, gi, G, row, slot
-                m += G
-                row += G
-                slot += 1
-        t = lambda a: torch.from_numpy(a).to(device)
-        self.batches = [] if not self.n_docs else [dict(
-            x=True, seg_doc=t(seg_doc), seg_index=t(seg_index), seg_count=t(seg_count), seg_base=t(seg_base),
-            doc_slot=t(doc_slot), n_blocks=nb, n_rows=row,
-            # granules {lo, tag, hi, tag} (uint32): [2][n_rows][KS + 1][4]
-            xchg=torch.zeros(2 * row * (self.KS + 1) * 4, dtype=torch.int32, device=device),
-            counter=torch.zeros(2 * slot, dtype=torch.int32, device=device),
-            error=torch.zeros(1, dtype=torch.int32, device=device),
-            placed=torch.zeros(max(slot, 1), dtype=torch.int32, device=device), docs=slot, proto=self.proto)]
-
-
-def gs_xsplit(doc_ptr, word_idx, counts, beta, K, gs_updates, params, gamma, cphi, lik, alpha_ss, iters, batch,
-              dbg=None, ent_base=None):
-    """One launch of the XCD-split E-step over a GSXSplitPlan batch.  dbg: optional int64[8] phase timer
-    of member 0 of the first document (word phase + reduction, publish -> gathered, refresh, chunks)."""
-    D = doc_ptr.numel() - 1
-    nnz = word_idx.numel()
-    V, KS = beta.shape
-    dev = beta.device
-    nb = batch["n_blocks"]
-    if gs_xsplit_rows(KS) <= 0 or not (0 < K <= KS) or not (1 <= int(gs_updates) <= 32):
-        raise ValueError("gs_xsplit: KS, K or gs_updates out of range")
-    for k in ("seg_doc", "seg_index", "seg_count", "seg_base", "doc_slot"):
-        _chk(batch[k], torch.int32, k, (nb,), dev)
-    exp_lib().gs_xsplit(
-        _chk(doc_ptr, torch.int32, "doc_ptr", (D + 1,), dev), _chk(word_idx, torch.int32, "word_idx", (nnz,), dev),
-        _chk(counts, torch.float32, "counts", (nnz,), dev), _chk(beta, torch.float64, "beta", (V, KS), dev),
-        int(K), int(KS), int(gs_updates), _params_ptr(params, dev) or _bad("params"),
-        _chk(gamma, torch.float64, "gamma", (D, KS), dev), _cphi_ptr(cphi, nnz, KS, dev, ent_base),
-        _chk(lik, torch.float64, "lik", (D,), dev), _chk(alpha_ss, torch.float64, "alpha_ss", (D,), dev),
-        _chk(iters, torch.int32, "iters", (D,), dev),
-        batch["seg_doc"].data_ptr(), batch["seg_index"].data_ptr(), batch["seg_count"].data_ptr(),
-        batch["seg_base"].data_ptr(), batch["doc_slot"].data_ptr(), int(nb), int(batch["n_rows"]),
-        _chk(batch["xchg"], torch.int32, "xchg", (2 * batch["n_rows"] * (KS + 1) * 4,), dev),
-        _chk(batch["counter"], torch.int32, "counter", (2 * batch["docs"],), dev), int(batch["docs"]),
-        _chk(batch["error"], torch.int32, "error", (1,), dev), int(batch["proto"]),
-        _chk(batch["placed"], torch.int32, "placed", None, dev), _stream(),
-        0 if dbg is None else _chk(dbg, torch.int64, "dbg", (8,), dev))
-
-
 class GSPlan:
     """Length buckets of the fp64 block Gauss-Seidel E-step: (variant, int32 doc order) per launch.
 
@@ -1164,7 +1038,7 @@ class GSPlan:
                     (GS_SMALL, None, GS_SMALL_MAX))
 
     def __init__(self, lengths, KS: int, gs_updates: int, device, split_min: Optional[int] = None,
-                 doc_range=None, xsplit: Optional[dict] = None):
+                 doc_range=None):
         import numpy as np
         self.KS = int(KS)
         L = np.asarray(lengths, dtype=np.int64)
@@ -1188,18 +1062,6 @@ class GSPlan:
         if int(gs_updates) > gs_split_umax(KS):
             split_min = 0       # KS <= 32: the split kernel's chunk tables live in LDS (U <= 32)
         self.split = None
-        # xsplit = {docs: N, members: G, proto: P} (even KS <= 32): the N longest documents over the CUs of
-        # one XCD each (gs_xsplit; an experiment, off by default: profiles/r5_xcd_split.md)
-        xs = dict(xsplit or {})
-        nx = int(xs.pop("docs", 0)) if KS <= 32 and KS % 2 == 0 and int(gs_updates) <= 32 else 0
-        if nx > 0 and L.size and gs_xsplit_rows(KS) > 0:
-            head = order[:nx + 16]
-            head = head[L[head] > 2 * int(gs_updates)]
-            xp = GSXSplitPlan(head, L, KS, gs_updates, device, limit=nx, **xs) if head.size else None
-            if xp is not None and xp.n_docs:
-                self.split = xp
-                order = order[~np.isin(order, np.asarray(sorted(xp.segments), np.int64))]
-                split_min = 0
         if split_min > 0 and (L > split_min).any():
             m = L[order] > split_min
             sp = GSSplitPlan(order[m], L, KS, gs_updates, device)

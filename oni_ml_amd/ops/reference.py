@@ -5,7 +5,7 @@ vector per variational iteration; the closed-form likelihood and lda-c's converg
 documents with per-document convergence masks, plus the suff-stats and M-step.  It is a test rehearsal
 engine only -- the one whose multi-rank statistics can fold bitwise like one process
 (ONI_DIST_DETERMINISTIC=chain, tests/test_sharded_pipeline.py).  The MI355X engine is the fp64 block
-Gauss-Seidel of csrc/hip/lda_gs64.hip and the CPU engine the lda-c Gauss-Seidel of
+Gauss-Seidel of csrc/hip/lda_gs64.hip (kernels: gs_*.hip) and the CPU engine the lda-c Gauss-Seidel of
 csrc/native/lda_ref.cpp; both are checked against lda_ref.cpp, not against this module.
 """
 from __future__ import annotations

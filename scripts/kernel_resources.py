@@ -2,7 +2,7 @@
 """Per-kernel register / scratch / LDS / occupancy of a HIP source, from the compiler's
 kernel-resource-usage remarks (no GPU needed):
 
-  python scripts/kernel_resources.py csrc/hip/lda_gs64.hip [--filter 'gs_smallw|gs_team'] [--json OUT]
+  python scripts/kernel_resources.py csrc/hip/gs_team.hip [--filter 'gs_team<100'] [--json OUT]
 """
 import argparse
 import json

@@ -5,7 +5,7 @@ The reference core (oni-lda-c) computes in double with 
 Gauss-Seidel schedule.  This script trains the SAME corpus (bench.py's 1-day synthetic netflow,
 seed 0) from the SAME random init with several engines and compares what the pipeline consumes:
 
-  hip    fp64 block Gauss-Seidel (HIP kernels, csrc/hip/lda_gs64.hip; the bench path): gamma
+  hip    fp64 block Gauss-Seidel (HIP kernels, csrc/hip/lda_gs64.hip and gs_*.hip; the bench path): gamma
          refreshed every ceil(n/32) words, lda-c's per-word schedule for documents <= 32 words
   torch  fp64 Jacobi E-step (PyTorch on the host CPU, ops/reference.py)
   cpu    fp64 Gauss-Seidel E-step, a literal transcription of lda-c's lda_inference

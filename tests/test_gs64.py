@@ -490,55 +490,68 @@ def test_large_u_at_narrow_topics_plans_table_free_kernels():
         LDAEngine(c, 20, st, backend="hip", seed=0, precision="fp64")
 
 
-@pytest.mark.parametrize("K,xs", [
-    (20, dict(docs=3)),                                  # LDS-minimum members, placement-checked stores
-    (20, dict(docs=3, proto=0)),                         # write-through stores only
-    (20, dict(docs=4, members=11)),                      # more members than the LDS needs
-    (8, dict(docs=2, members=3)),                        # > 64 words of a chunk per member
-    (32, dict(docs=2)),                                  # one member part per column (KS + 1 = 33)
-])
-def test_xsplit_documents_match_oracle(K, xs):
-    """gs_xsplit (csrc/hip/experimental/lda_xsplit.hip: one document over one-wave members of one XCD, beta rows resident
-    in LDS, 16-byte self-tagged granules) against the oracle at 1e-10, every member replaying the same
-    refresh; graph replay moves the launch epoch on.  The experimental module is built only on request
-    (`python -m oni_ml_amd._build exp`; measured not faster, profiles/r5_xcd_split.md)."""
+def _compiled_ks():
     from oni_ml_amd.ops import hip as H
-    if not H.exp_available():
-        pytest.skip("experimental module _onihip_exp not built (python -m oni_ml_amd._build exp)")
-    rng = np.random.default_rng(K + 7)
-    V, D = 40000, 260
-    lens = np.minimum(rng.zipf(1.5, D), 200)
-    lens[:6] = [30000, 20000, 12000, 9100, 5000, 3100]
-    lens[9] = 0
+    return H.compiled_ks()
+
+
+def _bucket_corpus(V=3000, D=130):
+    """A document in every length bucket of every plan (tiny, small, one wave, 4 waves, 8 waves or split) and an
+    empty one; distinct words per document, counts 1-3, ~9,000 entries."""
+    rng = np.random.default_rng(11)
+    lens = np.minimum(rng.zipf(1.5, D), 60)
+    head = [2600, 2100, 700, 300, 100, 40, 9, 6, 3, 1, 0]
+    lens[:len(head)] = head
     ptr = np.concatenate([[0], np.cumsum(lens)])
     words = np.concatenate([rng.choice(V, n, replace=False) for n in lens]).astype(np.int32)
     counts = rng.integers(1, 4, words.size)
-    c = Corpus(ptr.astype(np.int64), words, counts.astype(np.int64), V)
-    lb = _log_beta(V, K, seed=5)
-    for vconv in (-1e30, 1e-6):
-        st = LDASettings(var_max_iter=5, var_converged=vconv)
-        ref = _oracle(c, lb, 0.33, st, 32)
-        eng, sc = _gpu_estep(c, K, lb, 0.33, LDASettings(var_max_iter=5, var_converged=vconv), 32, xsplit=xs)
-        sp = eng.gs_plan.split
-        assert sp is not None and sp.n_docs == xs["docs"]
-        (b,) = sp.batches
-        assert b.get("x") and int(b["error"].item()) == 0
-        if xs.get("proto", 1) == 1:
-            assert set(b["placed"].cpu().tolist()) <= {0, 1}
-        full = lens > 0
-        it = eng.iters.cpu().numpy()
-        same = (it == ref["iters"]) | ~full
-        if vconv < 0:
-            assert same.all()
-        else:
-            assert same.mean() > 0.99 and same[:6].all()
-        assert _rel(eng.gamma[:, :K].cpu().numpy()[same], ref["gamma"][same], 1e-12) < 1e-10
-        assert _rel(eng.lik.cpu().numpy()[same], ref["doc_likelihood"][same], 1.0) < 1e-10
-        if vconv < 0:
-            cw = eng._cw_local[:, :K].cpu().numpy()
-            assert _rel(cw, np.ascontiguousarray(ref["class_word"].T), 1e-30) < 1e-10
-            assert abs(sc[0] - ref["likelihood"]) / abs(ref["likelihood"]) < 1e-11
-            g1 = eng.gamma.clone()
-            eng.e_step()
-            torch.cuda.synchronize()
-            assert torch.equal(g1, eng.gamma)
+    return Corpus(ptr.astype(np.int64), words, counts.astype(np.int64), V), lens
+
+
+def _expected_buckets(H, KS, U, split):
+    """Bucket variants GSPlan makes of _bucket_corpus (ops/hip.py EDGES, EDGES_NARROW, wide_u_edges,
+    narrow_wide_u_edges); split: the two documents past 2,048 words are on gs_split instead of the 8-wave bucket."""
+    if KS <= 32:
+        return ({H.GS_TINY, H.GS_SMALL, H.GS_TEAM1, H.GS_TEAM4, H.GS_TEAM8} if U <= 32 else
+                {H.GS_TINY, H.GS_CHAIN, H.GS_TEAM4, H.GS_TEAM8})
+    # (U = 64: gs_chain's range at KS > 32, 256 < n <= 2 U, is empty)
+    return {H.GS_TINY, H.GS_SMALL, H.GS_TEAM4} | (set() if split else {H.GS_TEAM8})
+
+
+@pytest.mark.parametrize("K", _compiled_ks())
+def test_every_compiled_ks_runs_every_bucket(K, monkeypatch):
+    """Every compiled row stride KS (K = KS) through every family launcher's KS switch: at U = 32 the LDS-table
+    kernels (gs_tiny, gs_small / gs_smallw, gs_team<KS, 1>, gs_wteam, gs_wsteam at KS <= 32; gs_team<KS, 4, 3, GM>
+    and gs_splitw or gs_team<KS, 8> at KS > 32), at U = 64 the kernels with their tables in the c.phi rows
+    (gs_chain and the GMT teams at KS <= 32; gs_splitw<52, 64> or its tab scratch, or gs_team<KS, 8, 1, GMT> with
+    the split off, at KS > 32).  A (KS, variant) pair missing from a switch throws or leaves its documents
+    unwritten here, not when a corpus of that shape first arrives."""
+    from oni_ml_amd.ops import hip as H
+    assert K in H.compiled_ks()
+    c, lens = _bucket_corpus()
+    lb = _log_beta(c.num_terms, K, seed=5)
+    full = lens > 0      # the empty document's 0/0 convergence test may stop a sweep apart (see above)
+    for U in (32, 64):
+        ref = _oracle(c, lb, 0.33, LDASettings(var_max_iter=3, var_converged=-1e30), U)
+        cw_ref = np.ascontiguousarray(ref["class_word"].T)
+        for split in ((True, False) if K > 32 else (False,)):
+            if K > 32 and not split:
+                monkeypatch.setenv("ONI_GS_SPLIT_MIN", "0")
+            else:
+                monkeypatch.delenv("ONI_GS_SPLIT_MIN", raising=False)
+            eng, _ = _gpu_estep(c, K, lb, 0.33, LDASettings(var_max_iter=3, var_converged=-1e30), U)
+            assert eng.KS == K
+            kinds = {v for v, _ in eng.gs_plan.plan}
+            assert kinds == _expected_buckets(H, K, U, split), (K, U, split, kinds)
+            sp = eng.gs_plan.split
+            if split:
+                assert sp is not None and sorted(sp.segments) == [0, 1]
+                assert int(sum(b["error"].item() for b in sp.batches)) == 0
+            else:
+                assert sp is None
+            assert np.array_equal(eng.iters.cpu().numpy()[full], ref["iters"][full]), (K, U, split)
+            assert _rel(eng.gamma[:, :K].cpu().numpy(), ref["gamma"], 1e-12) < 1e-10, (K, U, split)
+            assert _rel(eng.lik.cpu().numpy(), ref["doc_likelihood"], 1.0) < 1e-10, (K, U, split)
+            assert _rel(eng._cw_local[:, :K].cpu().numpy(), cw_ref, 1e-30) < 1e-10, (K, U, split)
+
+
