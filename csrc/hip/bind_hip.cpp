@@ -174,6 +174,17 @@ PYBIND11_MODULE(_onihip, m) {
     oni::launch_select_lowest(a, max_blocks, S(stream));
   });
 
+  m.def("host_summary", [](u doc_a, u score_a, u doc_b, u score_b, int64_t n, int64_t D, double tol, u events,
+                           u flagged, u min_key, u worst, u skipped, bool fold, u stats, int max_blocks, u stream) {
+    if (n <= 0 || n >= ((int64_t)1 << 31) || D <= 0 || D >= ((int64_t)1 << 31))
+      throw std::runtime_error("host_summary: n or D outside 1 .. 2^31 - 1");
+    oni::HostSummaryArgs a{P<const int>(doc_a), P<const double>(score_a), P<const int>(doc_b),
+                           P<const double>(score_b), n, D, tol, P<unsigned>(events), P<unsigned>(flagged),
+                           P<unsigned long long>(min_key), P<unsigned>(worst), P<unsigned>(skipped), fold ? 1 : 0,
+                           P<unsigned long long>(stats)};
+    oni::launch_host_summary(a, max_blocks, S(stream));
+  });
+
   m.def("string_entropy", [](u bytes, u offsets, int64_t n, u table, int64_t table_len, u out, int max_blocks,
                              u stream) {
     if (n < 0 || table_len < 2 || max_blocks < 0) throw std::runtime_error("string_entropy: bad sizes");

@@ -241,6 +241,29 @@ int select_result_word();
 // max_blocks: cap on the workgroups per launch (0: 2048); more tiles than that are grid-strided
 void launch_select_lowest(const SelectArgs& a, int max_blocks, hipStream_t s);
 
+// Host report (host_summary.hip): per document the number of scored sides, of sides under TOL, the lowest
+// non-NaN score (as its order key) and the lowest side number 2 * event + side that attains it.
+constexpr int kHostSummaryStats = 3;   // stats words: atomics issued for the counts, for min_key, for worst
+struct HostSummaryArgs {
+  const int* doc_a;            // [n] document row of side a, or -1
+  const double* score_a;       // [n]
+  const int* doc_b;            // [n] side b (flow: the destination) or nullptr
+  const double* score_b;       // [n] or nullptr, with doc_b
+  int64_t n;                   // events, 0 < n < 2^31 (a side number 2 n + 1 fits 32 bits)
+  int64_t D;                   // documents, 0 < D < 2^31; a row outside [0, D) is a skipped side
+  double tol;
+  unsigned* events;            // [D] sides of the document
+  unsigned* flagged;           // [D] of those, the sides with score < tol
+  unsigned long long* min_key; // [D] lowest order key of the non-NaN scores; all-ones: none
+  unsigned* worst;             // [D] lowest side number whose key is min_key; all-ones: none
+  unsigned* skipped;           // [1] sides whose row is no document
+  int fold;                    // non-zero: a wave folds the documents that repeat in it (0: one atomic per side)
+  unsigned long long* stats;   // [kHostSummaryStats] or nullptr: atomics issued (measurement only)
+};
+// Starts the outputs at 0 / 0 / all-ones / all-ones / 0 (and stats at 0) itself, then two grid-stride passes.
+// max_blocks: cap on the workgroups per launch (0: 2048)
+void launch_host_summary(const HostSummaryArgs& a, int max_blocks, hipStream_t s);
+
 // Byte entropy of every string of a batch (string_entropy.hip): out[i] = (t[n] - sum_b t[c_b]) / n over the
 // bytes [offsets[i], offsets[i + 1]) of `bytes`, t = table (c log2 c, host-built), 0 for n <= 1.
 struct StringEntropyArgs {

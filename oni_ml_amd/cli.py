@@ -107,6 +107,9 @@ def cmd_ml_ops(argv):
     ap.add_argument("maxresults", nargs="?", default=None, type=int,
                     help="write only the N most suspicious events under TOL (-1: no limit)")
     ap.add_argument("--max-results", type=int, default=None, help="as MAXRESULTS; wins over the positional")
+    ap.add_argument("--host-report", type=int, default=None, metavar="N",
+                    help="also write <type>_hosts.csv: the day's hosts ranked by their lowest score, one line per host "
+                         "(-1: every host with an event under TOL; N: the N lowest; one process only)")
     ap.add_argument("--conf", default=knobs.get("ONI_CONF", "/etc/duxbay.conf"))
     ap.add_argument("--lpath")
     ap.add_argument("--flow-path")
@@ -146,6 +149,8 @@ def cmd_ml_ops(argv):
     from . import config as CFG
     if a.dsource == "proxy" and (a.gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1 or a.hdfs):
         raise ValueError(CFG.PROXY_ONE_PROCESS)     # before a process group is asked for
+    if a.host_report and (a.gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1 or a.hdfs):
+        raise ValueError(CFG.HOST_REPORT_ONE_PROCESS)
 
     def resolve(world):
         return CFG.resolve(a.fdate, a.dsource, tol=float(a.tol) if a.tol is not None else None, conf_path=a.conf,
@@ -156,7 +161,7 @@ def cmd_ml_ops(argv):
                            compat=a.compat, seed=a.seed, start=a.start, resume=a.resume, threads=a.threads,
                            write_doc_wc=a.keep_doc_wc, word_assignments=a.word_assignments,
                            rank_gamma=a.rank_gamma, verbose=not a.quiet, cuts=a.cuts, hdfs=a.hdfs or None,
-                           hadoop=a.hadoop)
+                           hadoop=a.hadoop, host_report=a.host_report)
     # one process, fresh run: the day's inputs are read on a thread while torch imports
     # (pipeline/prefetch.py); the load stage takes the result
     from .pipeline import prefetch

@@ -31,6 +31,9 @@ ENV_KEYS = ("FLOW_PATH", "DNS_PATH", "PROXY_PATH", "HPATH", "LPATH", "LUSER", "T
 # proxy has no multi-rank, sharded or HDFS-staged form
 PROXY_ONE_PROCESS = "proxy runs on one process: launch it without torchrun, with --gpus 1 and without --hdfs"
 
+# the host report folds one process's scored sides: no multi-rank, sharded or HDFS-staged form yet
+HOST_REPORT_ONE_PROCESS = "--host-report runs on one process: launch it without torchrun, with --gpus 1 and without --hdfs"
+
 _VAR = re.compile(r"\$\{([A-Za-z_][A-Za-z0-9_]*)\}|\$([A-Za-z_][A-Za-z0-9_]*)")
 
 
@@ -81,6 +84,8 @@ class RunConfig:
     dsource: str = "flow"                 # flow | dns | proxy
     tol: float = 1e-20
     max_results: int = -1                 # MAXRESULTS: write only the N lowest scores under TOL; -1: no limit
+    host_report: int = 0                  # --host-report: also write <type>_hosts.csv; 0: off, -1: every host with a
+                                          # side under TOL, N >= 1: the N hosts with the lowest scores
     lpath: str = ""                       # local working dir (reference: ${LUSER}/ml/${FDATE})
     hpath: str = ""                       # HDFS dir in the reference; unused unless set (optional copy target)
     flow_path: str = ""
@@ -149,6 +154,10 @@ class RunConfig:
             raise ValueError("topics must be >= 1")
         if self.max_results != -1 and self.max_results < 1:
             raise ValueError(f"MAXRESULTS must be -1 (no limit) or >= 1, got {self.max_results}")
+        if self.host_report < -1:
+            raise ValueError(f"--host-report must be 0 (off), -1 (every flagged host) or >= 1, got {self.host_report}")
+        if self.host_report and (self.gpus > 1 or self.hdfs):
+            raise ValueError(HOST_REPORT_ONE_PROCESS)
         return self
 
     def to_dict(self) -> dict:

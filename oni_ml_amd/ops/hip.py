@@ -302,6 +302,72 @@ def select_lowest(key, flag, limit, max_blocks: int = 0, with_count: bool = Fals
     return (out[:m], flagged) if with_count else out[:m]
 
 
+def host_summary(doc_a, score_a, doc_b, score_b, num_docs, tol, max_blocks: int = 0, fold: bool = True,
+                 stats: bool = False):
+    """Per document the scored sides folded (csrc/hip/host_summary.hip; ``ops.reference.host_summary`` is the
+    twin): ``(events int64 [D], flagged int64 [D], min_score float64 [D], worst int64 [D], skipped int)``.
+
+    Event i has the side a ``(doc_a[i], score_a[i])`` and, when ``doc_b`` / ``score_b`` are given, the side b;
+    side number ``2 i + side``.  ``doc``: int32 document row in ``[0, num_docs)`` or -1 (no document: the side
+    is only counted in ``skipped``).  ``events``: sides of the document; ``flagged``: of those, the sides with
+    score < ``tol``; ``min_score``: their lowest non-NaN score in the order of ``sortgroup.f64_order_keys``
+    (-0.0 below +0.0), +inf when there is none; ``worst``: the lowest side number that attains it, -1 when
+    there is none.  Host reads: the bounds of the rows before the launch, ``skipped`` after it.
+    ``max_blocks``: cap on the workgroups per launch (tests: a small cap makes the grid-stride loops wrap).
+    ``fold``: a wave folds the documents that repeat in it before it adds (False: one atomic per side, 10 to 127
+    times slower when one document has half of the sides, profiles/host_report.md) -- the result does not depend
+    on it.  ``stats``: also return, as a sixth value, the atomics issued ``(counts, min_key, worst)``
+    (measurement: scripts/host_report_bench.py)."""
+    import operator
+    if not isinstance(max_blocks, int) or isinstance(max_blocks, bool) or max_blocks < 0:
+        raise ValueError(f"max_blocks must be a non-negative int, got {max_blocks!r}")
+    D = operator.index(num_docs)
+    if D < 0 or D >= 1 << 31:
+        raise ValueError(f"num_docs must be in [0, 2^31), got {D}")
+    if (doc_b is None) != (score_b is None):
+        raise ValueError("host_summary: doc_b and score_b go together")
+    if not isinstance(doc_a, torch.Tensor) or doc_a.dim() != 1:
+        raise ValueError("doc_a: expected a 1-D tensor")
+    n = doc_a.numel()
+    dev = doc_a.device
+    if n >= 1 << 31:
+        raise ValueError(f"host_summary: {n} events, side numbers are 32-bit (n < 2^31)")
+    two = doc_b is not None
+    ptr = [_chk(doc_a, torch.int32, "doc_a", (n,), dev), _chk(score_a, torch.float64, "score_a", (n,), dev),
+           _chk(doc_b, torch.int32, "doc_b", (n,), dev) if two else 0,
+           _chk(score_b, torch.float64, "score_b", (n,), dev) if two else 0]
+    L = lib()
+    # index bounds (host check before the scatter kernel touches memory)
+    if n:
+        for name, idx in (("doc_a", doc_a), ("doc_b", doc_b)):
+            if idx is not None and (int(idx.max()) >= D or int(idx.min()) < -1):
+                raise ValueError(f"{name}: index out of range")
+    sides = n * (2 if two else 1)
+    if n == 0 or D == 0:      # nothing to fold: every side (D == 0: all at -1, checked above) is skipped
+        out = (torch.zeros(D, dtype=torch.int64, device=dev), torch.zeros(D, dtype=torch.int64, device=dev),
+               torch.full((D,), float("inf"), dtype=torch.float64, device=dev),
+               torch.full((D,), -1, dtype=torch.int64, device=dev), sides)
+        return out + ((0, 0, 0),) if stats else out
+    events = torch.empty(D, dtype=torch.int32, device=dev)
+    flagged = torch.empty(D, dtype=torch.int32, device=dev)
+    min_key = torch.empty(D, dtype=torch.int64, device=dev)
+    worst = torch.empty(D, dtype=torch.int32, device=dev)
+    tail = torch.empty(1 + 3, dtype=torch.int64, device=dev)      # skipped (low 32 bits), the stats words
+    L.host_summary(*ptr, int(n), int(D), float(tol), events.data_ptr(), flagged.data_ptr(), min_key.data_ptr(),
+                   worst.data_ptr(), tail.data_ptr(), bool(fold), tail[1:].data_ptr() if stats else 0,
+                   int(max_blocks), _stream())
+    u32 = lambda t: t.to(torch.int64) & 0xFFFFFFFF      # noqa: E731 -- the kernels' counters are unsigned
+    w = u32(worst)
+    # the order key back to the double: keys with the top bit set are the non-negatives (clear it), the
+    # others the negatives with every bit flipped; all-ones: no non-NaN score
+    bits = torch.where(min_key < 0, min_key ^ (-1 << 63), ~min_key)
+    min_score = torch.where(min_key == -1, torch.full_like(bits, 0x7FF0000000000000), bits).view(torch.float64)
+    host = tail.cpu().tolist()
+    out = (u32(events), u32(flagged), min_score, torch.where(w == 0xFFFFFFFF, torch.full_like(w, -1), w),
+           host[0] & 0xFFFFFFFF)
+    return out + (tuple(host[1:]),) if stats else out
+
+
 def string_entropy(bytes_u8, offsets, max_blocks: int = 0):
     """float64 [n] Shannon entropy of the byte strings [offsets[i], offsets[i + 1]) of ``bytes_u8`` (uint8, on
     the GPU), bit for bit ``ops.reference.string_entropy`` (csrc/hip/string_entropy.hip).  ``offsets``: int64

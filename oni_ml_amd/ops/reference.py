@@ -157,6 +157,70 @@ def select_lowest(key, flag, limit, with_count: bool = False):
     return (out, flagged) if with_count else out
 
 
+def host_summary(doc_a, score_a, doc_b, score_b, num_docs, tol, max_blocks: int = 0):
+    """Torch twin of ``ops.hip.host_summary`` (csrc/hip/host_summary.hip) on any device, same results:
+    ``(events int64 [D], flagged int64 [D], min_score float64 [D], worst int64 [D], skipped int)``.
+
+    From the sortgroup primitives, without atomics: the sides (side number ``2 i + side``) that name a document
+    are sorted stably by order key (every NaN last) and then stably by document, which orders them by
+    (document, order key, side number); run starts and a prefix sum give the counts per document, and the first
+    side of every run is the document's lowest non-NaN score and the lowest side number that attains it (a NaN
+    there: the document has none).  ``max_blocks`` is accepted and ignored (the kernel's launch cap)."""
+    import operator
+
+    from . import sortgroup as SG
+    D = operator.index(num_docs)
+    if D < 0 or D >= 1 << 31:
+        raise ValueError(f"num_docs must be in [0, 2^31), got {D}")
+    if not isinstance(max_blocks, int) or isinstance(max_blocks, bool) or max_blocks < 0:
+        raise ValueError(f"max_blocks must be a non-negative int, got {max_blocks!r}")
+    if (doc_b is None) != (score_b is None):
+        raise ValueError("host_summary: doc_b and score_b go together")
+    if doc_a.dim() != 1 or doc_a.dtype != torch.int32 or score_a.dtype != torch.float64 or score_a.shape != doc_a.shape:
+        raise ValueError("host_summary: doc_a int32 [n], score_a float64 [n]")
+    n = doc_a.numel()
+    if n >= 1 << 31:
+        raise ValueError(f"host_summary: {n} events, side numbers are 32-bit (n < 2^31)")
+    two = doc_b is not None
+    if two and (doc_b.dtype != torch.int32 or score_b.dtype != torch.float64 or doc_b.shape != doc_a.shape
+                or score_b.shape != doc_a.shape):
+        raise ValueError("host_summary: doc_b int32 [n], score_b float64 [n]")
+    dev = doc_a.device
+    if two:      # interleaved: position 2 i + side
+        doc = torch.stack([doc_a, doc_b], 1).reshape(-1).to(torch.int64)
+        sc = torch.stack([score_a, score_b], 1).reshape(-1)
+    else:
+        doc, sc = doc_a.to(torch.int64), score_a
+    if n and (int(doc.max()) >= D or int(doc.min()) < -1):
+        raise ValueError("host_summary: index out of range")
+    events = torch.zeros(D, dtype=torch.int64, device=dev)
+    flagged = torch.zeros(D, dtype=torch.int64, device=dev)
+    min_score = torch.full((D,), float("inf"), dtype=torch.float64, device=dev)
+    worst = torch.full((D,), -1, dtype=torch.int64, device=dev)
+    num = torch.arange(doc.numel(), device=dev, dtype=torch.int64) * (1 if two else 2)      # side numbers
+    num, _ = SG.compact(num, doc >= 0)
+    skipped = doc.numel() - num.numel()
+    if num.numel() == 0:
+        return events, flagged, min_score, worst, skipped
+    pos = num if two else num >> 1
+    doc, sc = SG.gather(doc, pos), SG.gather(sc, pos)
+    by_key = SG.sort_stable(SG.f64_order_keys(sc))[1]      # NaN (the canonical positive one) after +inf
+    perm = SG.gather(by_key, SG.sort_stable(SG.gather(doc, by_key))[1])
+    sd = SG.gather(doc, perm)
+    grp, G = SG.run_ids(sd)
+    st = SG.run_starts(grp, G)
+    rows = SG.gather(sd, st[:-1])
+    first = SG.gather(perm, st[:-1])
+    s0 = SG.gather(sc, first)
+    has = s0 == s0
+    under = torch.cumsum(SG.gather((sc < tol).to(torch.int64), perm), 0)
+    events.index_put_((rows,), st[1:] - st[:-1])
+    flagged.index_put_((rows,), SG.diff_prepend0(SG.gather(under, st[1:] - 1)))
+    min_score.index_put_((rows,), torch.where(has, s0, torch.full_like(s0, float("inf"))))
+    worst.index_put_((rows,), torch.where(has, SG.gather(num, first), torch.full_like(first, -1)))
+    return events, flagged, min_score, worst, skipped
+
+
 def entropy_table(max_len: int):
     """t[c] = c log2(c) for c = 0 .. max_len as float64 (t[0] = t[1] = 0): the one table both
     ``string_entropy`` here and the HIP kernel (csrc/hip/string_entropy.hip) read, so neither side's log

@@ -208,6 +208,34 @@ def flagged_text(written: int, below_tol: int, limit, what: str, tol) -> str:
     return f"{written} of the {below_tol} {what} with score < {tol} (MAXRESULTS {limit})"
 
 
+def write_host_report(cfg, tables: ModelTables, doc_a, score_a, doc_b, score_b, row_cols, sep: str = ",",
+                      log=print) -> dict:
+    """--host-report: ``<type>_hosts.csv`` next to the results file, one line per host with a side under TOL,
+    ascending by the host's lowest score (``scorer.rank_hosts``; ``cfg.host_report`` hosts, -1: all of them):
+    host, sides, sides under TOL, lowest score, for two-sided events ``src`` / ``dst`` (the side that scored
+    it), then that event's row exactly as the results file writes it -- ``row_cols(rows)`` is the scorer's
+    column list for the given event rows.  Folds every scored side of the day, whatever MAXRESULTS is.
+    ``doc_*`` / ``score_*``: θ row (-1: none) and score of every event's side(s), on the scoring device."""
+    from ..ops import native
+    from ..ops import sortgroup as SG
+    from ..score import scorer as S
+    D = len(tables.doc_names)
+    ev, fl, ms, worst, skipped = S.host_summary(doc_a, score_a, doc_b, score_b, D, cfg.tol)
+    hosts = S.rank_hosts(ms, fl, None if cfg.host_report < 0 else cfg.host_report)
+    h_t = torch.from_numpy(hosts).to(ms.device)
+    take = lambda t: SG.gather(t, h_t).cpu().numpy()      # noqa: E731
+    side = take(worst)
+    cols = [("dict", [tables.doc_names[d] for d in hosts.tolist()], np.arange(hosts.size, dtype=np.int32)),
+            ("int", take(ev).astype(np.int64)), ("int", take(fl).astype(np.int64)), ("java", take(ms))]
+    if doc_b is not None:
+        cols.append(("dict", ["src", "dst"], (side & 1).astype(np.int32)))
+    cols += row_cols((side >> 1).astype(np.int64))
+    out = os.path.join(cfg.lpath, f"{cfg.dsource}_hosts.csv")
+    native.lib().write_rows(out, None, cols, sep=sep, threads=cfg.threads, n=int(hosts.size))
+    log(f"{cfg.dsource}_post: {hosts.size} hosts with a score < {cfg.tol} written to {out}")
+    return dict(hosts=int(hosts.size), host_sides_skipped=int(skipped))
+
+
 def save_json(path: str, obj):
     with open(path, "w") as f:
         json.dump(obj, f, indent=1, default=lambda o: o.tolist() if hasattr(o, "tolist") else str(o))

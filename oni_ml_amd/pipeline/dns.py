@@ -127,6 +127,8 @@ def run(cfg, dist=None, device=None, log=print) -> dict:
                 res.update(score_dns(cfg, tab, top, tables, device, log, host=pre_host))
                 summary["scored"] = res.get("flagged")
                 summary["below_tol"] = res.get("below_tol")
+                if cfg.host_report:
+                    summary["hosts"], summary["host_sides_skipped"] = res.get("hosts"), res.get("host_sides_skipped")
         else:
             R.skip("dns_post")
     except BaseException:
@@ -177,24 +179,27 @@ def score_dns(cfg, tab: FD.DnsTable, top, tables: C.ModelTables, device, log=pri
         order, below = S.rank_flagged_counted(key, flag, limit)
     n = int(order.size)
     out = os.path.join(cfg.lpath, "dns_results.csv")
-    # the flagged rows' 8 input columns, dictionary-encoded by Arrow on a thread each (its kernels
-    # release the GIL)
-    from concurrent.futures import ThreadPoolExecutor
-    with ThreadPoolExecutor(len(FD.COLUMNS)) as ex:
-        enc = list(ex.map(lambda c: tab.take_encoded(c, order), FD.COLUMNS))
-    cols = [("dict", names, ids) for ids, names in enc]
     H = feat.host
+
+    def row_cols(order):
+        """The 16 columns of the given queries, in that order: their 8 input columns, dictionary-encoded by
+        Arrow on a thread each (its kernels release the GIL), then the features, the word and the score."""
+        from concurrent.futures import ThreadPoolExecutor
+        with ThreadPoolExecutor(len(FD.COLUMNS)) as ex:
+            enc = list(ex.map(lambda c: tab.take_encoded(c, order), FD.COLUMNS))
+        o_t = torch.from_numpy(order).to(sc.device)
+        return [("dict", names, ids) for ids, names in enc] + [
+            ("dict", H["domains"], H["domain_id"][order]),
+            ("dict", H["subdomains"], H["subdomain_id"][order]),
+            ("int", H["subdomain_length"][order].astype(np.int64)),
+            ("int", H["num_periods"][order].astype(np.int64)),
+            ("java", H["entropy"][order]),
+            ("int", H["top_domain"][order].astype(np.int64)),
+            ("dict", unames, inv[torch.from_numpy(order).to(inv.device)].cpu().numpy().astype(np.int32)),
+            ("java", sc[o_t].cpu().numpy()),
+        ]
+    cols = row_cols(order)
     o_t = torch.from_numpy(order).to(sc.device)
-    cols += [
-        ("dict", H["domains"], H["domain_id"][order]),
-        ("dict", H["subdomains"], H["subdomain_id"][order]),
-        ("int", H["subdomain_length"][order].astype(np.int64)),
-        ("int", H["num_periods"][order].astype(np.int64)),
-        ("java", H["entropy"][order]),
-        ("int", H["top_domain"][order].astype(np.int64)),
-        ("dict", unames, inv[torch.from_numpy(order).to(inv.device)].cpu().numpy().astype(np.int32)),
-        ("java", sc[o_t].cpu().numpy()),
-    ]
     from ..ops import native
     if multi:
         text, ends = native.lib().format_rows(None, cols, n=n, row_ends=True, threads=cfg.threads)
@@ -206,7 +211,8 @@ def score_dns(cfg, tab: FD.DnsTable, top, tables: C.ModelTables, device, log=pri
                     events=ctx.allreduce_int(int(feat.word_key.numel())))
     native.lib().write_rows(out, None, cols, threads=cfg.threads, n=n)
     log(f"dns_post: {C.flagged_text(n, below, limit, 'queries', cfg.tol)} written to {out}")
-    return dict(flagged=n, below_tol=below, events=int(feat.word_key.numel()))
+    hosts = C.write_host_report(cfg, tables, didx, sc, None, None, row_cols, log=log) if cfg.host_report else {}
+    return dict(flagged=n, below_tol=below, events=int(feat.word_key.numel()), **hosts)
 
 
 def synthetic_dns_corpus(events: int = 2_000_000, seed: int = 0, device=None, strict: bool = True, threads: int = 8,

@@ -173,6 +173,8 @@ def run(cfg, dist=None, device=None, log=print) -> dict:
                 res.update(score_flow(cfg, ft, tables, device, log, ip_rows=ip_rows))
                 summary["scored"] = res.get("flagged")
                 summary["below_tol"] = res.get("below_tol")
+                if cfg.host_report:
+                    summary["hosts"], summary["host_sides_skipped"] = res.get("hosts"), res.get("host_sides_skipped")
         else:
             R.skip("flow_post")
     except BaseException:
@@ -236,7 +238,8 @@ def score_flow(cfg, ft: FF.FlowTable, tables: C.ModelTables, device, log=print, 
     if cfg.strict and K != 20:
         raise ValueError("compat=strict scores over exactly 20 topics (flow_post_lda.scala:232)")
     model = S.TopicModel.build(th, ph, S.default_value("flow", K, cfg.strict), device)
-    sa, sb, key, flag = S.score(model, SG.gather(didx, feat.sip), w_src, SG.gather(didx, feat.dip), w_dst, cfg.tol)
+    d_src, d_dst = SG.gather(didx, feat.sip), SG.gather(didx, feat.dip)
+    sa, sb, key, flag = S.score(model, d_src, w_src, d_dst, w_dst, cfg.tol)
     qs = S.key_quantiles(key)
     limit = cfg.max_results if cfg.max_results > 0 else None      # MAXRESULTS: the `limit` lowest scores only
     if limit is None:
@@ -247,32 +250,37 @@ def score_flow(cfg, ft: FF.FlowTable, tables: C.ModelTables, device, log=print, 
     n = int(order.size)
     out = os.path.join(cfg.lpath, "flow_results.csv")
     # output columns: 27 raw + time + ibyt_bin + ipkt_bin + time_bin + word_port + ip_pair + src/dest word + scores
-    o_t = torch.from_numpy(order).to(device)
-    inv_src = SG.gather(inv[: src.numel()], o_t).cpu().numpy().astype(np.int32)
-    inv_dst = SG.gather(inv[src.numel():], o_t).cpu().numpy().astype(np.int32)
-    if unames is None:      # names only for the words of the flagged rows
-        need = np.unique(np.concatenate([inv_src, inv_dst]))
-        unames = ws.decode(uk_np[need])
-        inv_src = np.searchsorted(need, inv_src).astype(np.int32)
-        inv_dst = np.searchsorted(need, inv_dst).astype(np.int32)
-    sel = lambda t: SG.gather(t, o_t).cpu().numpy()
-    cols = [
-        ("table", ft.table, order),
-        ("java", sel(feat.time)),
-        ("int", sel(feat.ibyt_bin).astype(np.int64)),
-        ("int", sel(feat.ipkt_bin).astype(np.int64)),
-        ("int", sel(feat.time_bin).astype(np.int64)),
-        ("java", sel(feat.word_port)),
-        ("pair", ipn, sel(feat.sip).astype(np.int32), sel(feat.dip).astype(np.int32)),
-        ("dict", unames, inv_src),
-        ("dict", unames, inv_dst),
-        ("java", sel(sa)),
-        ("java", sel(sb)),
-    ]
+    def row_cols(order):
+        """The 37 columns of the given events, in that order."""
+        o_t = torch.from_numpy(order).to(device)
+        inv_src = SG.gather(inv[: src.numel()], o_t).cpu().numpy().astype(np.int32)
+        inv_dst = SG.gather(inv[src.numel():], o_t).cpu().numpy().astype(np.int32)
+        names = unames
+        if names is None:      # names only for the words of these rows
+            need = np.unique(np.concatenate([inv_src, inv_dst]))
+            names = ws.decode(uk_np[need])
+            inv_src = np.searchsorted(need, inv_src).astype(np.int32)
+            inv_dst = np.searchsorted(need, inv_dst).astype(np.int32)
+        sel = lambda t: SG.gather(t, o_t).cpu().numpy()      # noqa: E731
+        return [
+            ("table", ft.table, order),
+            ("java", sel(feat.time)),
+            ("int", sel(feat.ibyt_bin).astype(np.int64)),
+            ("int", sel(feat.ipkt_bin).astype(np.int64)),
+            ("int", sel(feat.time_bin).astype(np.int64)),
+            ("java", sel(feat.word_port)),
+            ("pair", ipn, sel(feat.sip).astype(np.int32), sel(feat.dip).astype(np.int32)),
+            ("dict", names, inv_src),
+            ("dict", names, inv_dst),
+            ("java", sel(sa)),
+            ("java", sel(sb)),
+        ]
+    cols = row_cols(order)
     from ..ops import native
     if multi:
         text, ends = native.lib().format_rows(None, cols, n=n, row_ends=True, threads=cfg.threads)
-        total = SIO.merge_sorted_rows(ctx, sel(key).astype(np.float64), text, ends, out, limit=limit)
+        key_o = SG.gather(key, torch.from_numpy(order).to(device)).cpu().numpy()
+        total = SIO.merge_sorted_rows(ctx, key_o.astype(np.float64), text, ends, out, limit=limit)
         below = ctx.allreduce_int(below)
         log(f"flow_post: {C.flagged_text(total, below, limit, 'events', cfg.tol)} written to {out} "
             f"({n} from rank {ctx.rank})")
@@ -280,7 +288,8 @@ def score_flow(cfg, ft: FF.FlowTable, tables: C.ModelTables, device, log=print, 
                     events=ctx.allreduce_int(int(feat.time.numel())), **qs)
     native.lib().write_rows(out, None, cols, threads=cfg.threads, n=n)
     log(f"flow_post: {C.flagged_text(n, below, limit, 'events', cfg.tol)} written to {out}")
-    return dict(flagged=n, below_tol=below, events=int(feat.time.numel()), **qs)
+    hosts = C.write_host_report(cfg, tables, d_src, sa, d_dst, sb, row_cols, log=log) if cfg.host_report else {}
+    return dict(flagged=n, below_tol=below, events=int(feat.time.numel()), **qs, **hosts)
 
 
 def synthetic_flow_corpus(events: int = 1_000_000, seed: int = 0, workdir: Optional[str] = None, device=None,

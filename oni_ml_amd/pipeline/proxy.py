@@ -110,6 +110,8 @@ def run(cfg, dist=None, device=None, log=print) -> dict:
                 res.update(score_proxy(cfg, tab, top, tables, device, log, host=pre_host))
                 summary["scored"] = res.get("flagged")
                 summary["below_tol"] = res.get("below_tol")
+                if cfg.host_report:
+                    summary["hosts"], summary["host_sides_skipped"] = res.get("hosts"), res.get("host_sides_skipped")
         else:
             R.skip("proxy_post")
     except BaseException:
@@ -147,15 +149,20 @@ def score_proxy(cfg, tab: FP.ProxyTable, top, tables: C.ModelTables, device, log
         order, below = S.rank_flagged_counted(key, flag, limit)
     n = int(order.size)
     out = os.path.join(cfg.lpath, "proxy_results.csv")
-    from concurrent.futures import ThreadPoolExecutor
-    with ThreadPoolExecutor(min(len(FP.COLUMNS), max(1, cfg.threads))) as ex:
-        enc = list(ex.map(lambda c: tab.take_encoded(c, order), FP.COLUMNS))
-    o_t = torch.from_numpy(order).to(sc.device)
-    cols = [("dict", names, ids) for ids, names in enc]
-    cols += [
-        ("dict", unames, SG.gather(inv, o_t).cpu().numpy().astype(np.int32)),
-        ("java", SG.gather(sc, o_t).cpu().numpy()),
-    ]
+
+    def row_cols(order):
+        """The 21 columns of the given requests, in that order."""
+        from concurrent.futures import ThreadPoolExecutor
+        with ThreadPoolExecutor(min(len(FP.COLUMNS), max(1, cfg.threads))) as ex:
+            enc = list(ex.map(lambda c: tab.take_encoded(c, order), FP.COLUMNS))
+        o_t = torch.from_numpy(order).to(sc.device)
+        return [("dict", names, ids) for ids, names in enc] + [
+            ("dict", unames, SG.gather(inv, o_t).cpu().numpy().astype(np.int32)),
+            ("java", SG.gather(sc, o_t).cpu().numpy()),
+        ]
+    cols = row_cols(order)
     native.lib().write_rows(out, None, cols, sep="\t", threads=cfg.threads, n=n)
     log(f"proxy_post: {C.flagged_text(n, below, limit, 'requests', cfg.tol)} written to {out}")
-    return dict(flagged=n, below_tol=below, events=int(feat.word_key.numel()))
+    hosts = (C.write_host_report(cfg, tables, didx, sc, None, None, row_cols, sep="\t", log=log)
+             if cfg.host_report else {})
+    return dict(flagged=n, below_tol=below, events=int(feat.word_key.numel()), **hosts)

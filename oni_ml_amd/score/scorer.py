@@ -104,6 +104,26 @@ def rank_flagged_counted(key: torch.Tensor, flag: torch.Tensor, limit: int):
     return SG.gather(sel, order).cpu().numpy().astype(np.int64), flagged
 
 
+def host_summary(doc_a, score_a, doc_b, score_b, num_docs: int, tol: float):
+    """The scored sides folded per document, ``(events, flagged, min_score, worst, skipped)`` -- device tensors
+    [num_docs] and an int (``ops.hip.host_summary`` on the GPU, ``ops.reference.host_summary`` elsewhere).
+    ``doc_*``: the θ row of every side's IP or -1; ``worst``: side number 2 * event + side of the lowest score."""
+    i32 = lambda t: None if t is None else t.to(torch.int32).contiguous()      # noqa: E731
+    f64 = lambda t: None if t is None else t.contiguous()                      # noqa: E731
+    if score_a.device.type == "cuda":
+        from ..ops import hip as H
+        return H.host_summary(i32(doc_a), f64(score_a), i32(doc_b), f64(score_b), int(num_docs), float(tol))
+    from ..ops.reference import host_summary as ref
+    return ref(i32(doc_a), f64(score_a), i32(doc_b), f64(score_b), int(num_docs), float(tol))
+
+
+def rank_hosts(min_score: torch.Tensor, flagged: torch.Tensor, limit: Optional[int] = None) -> np.ndarray:
+    """Document rows with at least one flagged side, ascending by their lowest score, ties to the lowest row
+    (int64 host array); ``limit``: only the first ``limit`` of them (the MAXRESULTS radix select and its tie
+    rule)."""
+    return rank_flagged(min_score, flagged > 0, limit)
+
+
 def lookup_sorted(keys_sorted: torch.Tensor, values_idx: torch.Tensor, query: torch.Tensor) -> torch.Tensor:
     """Map query keys through a sorted key table -> row index (or -1)."""
     if keys_sorted.numel() == 0:
