@@ -161,6 +161,18 @@ PYBIND11_MODULE(_onihip, m) {
     oni::launch_score_events(a, S(stream));
   });
 
+  m.def("ensemble_max", []() { return oni::kEnsembleMax; });
+  m.def("score_ensemble", [](u theta, u phi, int R, int K, double dflt, u doc_a, u word_a, u doc_b, u word_b,
+                             int64_t n, double tol, u score_a, u score_b, u key, u flag, u votes, int max_blocks,
+                             u stream) {
+    oni::EnsembleScoreArgs a{P<const double>(theta), P<const double>(phi), R, K, dflt,
+                             P<const int>(doc_a),    P<const int>(word_a), P<const int>(doc_b),
+                             P<const int>(word_b),   n,                    tol,
+                             P<double>(score_a),     P<double>(score_b),   P<double>(key),
+                             P<uint8_t>(flag),       P<uint8_t>(votes)};
+    oni::launch_score_ensemble(a, max_blocks, S(stream));
+  });
+
   m.def("select_tile", []() { return oni::kSelectTile; });
   m.def("select_work_words", [](int64_t n) { return oni::select_work_words(n); });
   m.def("select_result_word", []() { return oni::select_result_word(); });

@@ -219,6 +219,30 @@ struct ScoreArgs {
 };
 void launch_score_events(const ScoreArgs& a, hipStream_t s);
 
+// Ensemble scoring (score_ensemble.hip): the mean over R members of score_events' member score, summed in
+// member order and divided by (double)R; R = 1 is score_events bit for bit.
+constexpr int kEnsembleMax = 64;   // largest R
+struct EnsembleScoreArgs {
+  const double* theta;    // [D][R][K] the members' p(z|d), interleaved per document
+  const double* phi;      // [V][R][K] the members' p(w|z), interleaved per word
+  int R;                  // members, 1 <= R <= kEnsembleMax
+  int K;                  // topics summed
+  double dflt;            // value of the default vector used for misses (every member)
+  const int* doc_a;       // [n] doc index or -1
+  const int* word_a;      // [n] word index or -1
+  const int* doc_b;       // [n] (flow: destination side) or nullptr
+  const int* word_b;      // [n] or nullptr, with doc_b
+  int64_t n;              // 0 <= n < 2^31
+  double tol;
+  double* score_a;        // [n] ensemble score of side a
+  double* score_b;        // [n] or nullptr, with doc_b
+  double* key;            // [n] min(score_a, score_b) (or score_a)
+  uint8_t* flag;          // [n] key < tol
+  uint8_t* votes;         // [n] members whose own key (min of that member's side scores) is < tol
+};
+// max_blocks: cap on the workgroups (0: 8192); more events than the grid's lanes are grid-strided
+void launch_score_ensemble(const EnsembleScoreArgs& a, int max_blocks, hipStream_t s);
+
 // MAXRESULTS (select_lowest.hip): the rows that a stable ascending sort of the flagged keys puts first.
 constexpr int kSelectTile = 2048;      // rows of one tile (256 threads x 8 rows); tiles are fixed and contiguous
 constexpr int kSelectPasses = 6;       // radix digits of 11, 11, 11, 11, 11 and 9 bits, most significant first

@@ -97,6 +97,7 @@ def clean_workdir(lpath: str):
         for f in glob.glob(os.path.join(lpath, pat)):
             os.unlink(f)
     shutil.rmtree(os.path.join(lpath, ".stages"), ignore_errors=True)
+    shutil.rmtree(os.path.join(lpath, "ensemble"), ignore_errors=True)      # the members of an --ensemble run
 
 
 def cmd_ml_ops(argv):
@@ -110,6 +111,9 @@ def cmd_ml_ops(argv):
     ap.add_argument("--host-report", type=int, default=None, metavar="N",
                     help="also write <type>_hosts.csv: the day's hosts ranked by their lowest score, one line per host "
                          "(-1: every host with an event under TOL; N: the N lowest; one process only)")
+    ap.add_argument("--ensemble", type=int, default=None, metavar="R",
+                    help="score by the mean of R models fitted from the seeds --seed, --seed + 1, ... (1 <= R <= 64; "
+                         "default 1 or ENSEMBLE; one process only)")
     ap.add_argument("--conf", default=knobs.get("ONI_CONF", "/etc/duxbay.conf"))
     ap.add_argument("--lpath")
     ap.add_argument("--flow-path")
@@ -161,7 +165,11 @@ def cmd_ml_ops(argv):
                            compat=a.compat, seed=a.seed, start=a.start, resume=a.resume, threads=a.threads,
                            write_doc_wc=a.keep_doc_wc, word_assignments=a.word_assignments,
                            rank_gamma=a.rank_gamma, verbose=not a.quiet, cuts=a.cuts, hdfs=a.hdfs or None,
-                           hadoop=a.hadoop, host_report=a.host_report)
+                           hadoop=a.hadoop, host_report=a.host_report, ensemble=a.ensemble)
+    # --ensemble / ENSEMBLE (the site file and the environment set it too): refused here, before anything is
+    # written and before a process group is asked for
+    CFG.RunConfig.check_ensemble(resolve(1).ensemble, a.start, a.gpus, a.hdfs,
+                                 int(os.environ.get("WORLD_SIZE", "1")))
     # one process, fresh run: the day's inputs are read on a thread while torch imports
     # (pipeline/prefetch.py); the load stage takes the result
     from .pipeline import prefetch

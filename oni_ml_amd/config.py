@@ -26,13 +26,17 @@ from typing import Dict, List, Optional
 from .models.lda.settings import LDASettings
 
 ENV_KEYS = ("FLOW_PATH", "DNS_PATH", "PROXY_PATH", "HPATH", "LPATH", "LUSER", "TOL", "DUPFACTOR", "KRB_AUTH", "NODES",
-            "UINODE", "RPATH", "LDAPATH", "SPK_EXEC", "SPK_EXEC_MEM", "TOP1M", "CUT", "MAXRESULTS")
+            "UINODE", "RPATH", "LDAPATH", "SPK_EXEC", "SPK_EXEC_MEM", "TOP1M", "CUT", "MAXRESULTS", "ENSEMBLE")
 
 # proxy has no multi-rank, sharded or HDFS-staged form
 PROXY_ONE_PROCESS = "proxy runs on one process: launch it without torchrun, with --gpus 1 and without --hdfs"
 
 # the host report folds one process's scored sides: no multi-rank, sharded or HDFS-staged form yet
 HOST_REPORT_ONE_PROCESS = "--host-report runs on one process: launch it without torchrun, with --gpus 1 and without --hdfs"
+
+# the ensemble's members are fitted and scored by one process: no multi-rank, sharded or HDFS-staged form
+ENSEMBLE_ONE_PROCESS = "--ensemble runs on one process: launch it without torchrun, with --gpus 1 and without --hdfs"
+ENSEMBLE_MAX = 64
 
 _VAR = re.compile(r"\$\{([A-Za-z_][A-Za-z0-9_]*)\}|\$([A-Za-z_][A-Za-z0-9_]*)")
 
@@ -84,6 +88,8 @@ class RunConfig:
     dsource: str = "flow"                 # flow | dns | proxy
     tol: float = 1e-20
     max_results: int = -1                 # MAXRESULTS: write only the N lowest scores under TOL; -1: no limit
+    ensemble: int = 1                     # --ensemble / ENSEMBLE: score by the mean of this many models fitted from
+                                          # the seeds seed, seed + 1, ...; 1: one model, as ever
     host_report: int = 0                  # --host-report: also write <type>_hosts.csv; 0: off, -1: every host with a
                                           # side under TOL, N >= 1: the N hosts with the lowest scores
     lpath: str = ""                       # local working dir (reference: ${LUSER}/ml/${FDATE})
@@ -158,7 +164,21 @@ class RunConfig:
             raise ValueError(f"--host-report must be 0 (off), -1 (every flagged host) or >= 1, got {self.host_report}")
         if self.host_report and (self.gpus > 1 or self.hdfs):
             raise ValueError(HOST_REPORT_ONE_PROCESS)
+        self.check_ensemble(self.ensemble, self.start, self.gpus, self.hdfs)
         return self
+
+    @staticmethod
+    def check_ensemble(ensemble: int, start: str, gpus: int = 1, hdfs: bool = False, world: int = 1):
+        """The --ensemble rules, also applied by the command line before anything is written."""
+        if not 1 <= ensemble <= ENSEMBLE_MAX:
+            raise ValueError(f"--ensemble must be in [1, {ENSEMBLE_MAX}], got {ensemble}")
+        if ensemble == 1:
+            return
+        if gpus > 1 or world > 1 or hdfs:
+            raise ValueError(ENSEMBLE_ONE_PROCESS)
+        if start not in ("random", "seeded"):
+            raise ValueError("--ensemble needs a random or seeded start: every member would begin from the model "
+                             f"{start!r} and be the same model")
 
     def to_dict(self) -> dict:
         d = asdict(self)
@@ -205,6 +225,8 @@ def _apply(cfg: RunConfig, layer: Dict[str, object]):
         cfg.tol = float(layer["TOL"])
     if "MAXRESULTS" in layer and layer["MAXRESULTS"] not in ("", None):
         cfg.max_results = int(layer["MAXRESULTS"])
+    if "ENSEMBLE" in layer and layer["ENSEMBLE"] not in ("", None):
+        cfg.ensemble = int(layer["ENSEMBLE"])
     if "DUPFACTOR" in layer and layer["DUPFACTOR"] not in ("", None):
         cfg.dupfactor = int(layer["DUPFACTOR"])
     if "CUT" in layer and isinstance(layer["CUT"], str) and layer["CUT"].strip():

@@ -260,6 +260,83 @@ def score_events(theta, phi, K, dflt, doc_a, word_a, doc_b, word_b, tol):
     return sa, sb, key, flag
 
 
+from ..config import ENSEMBLE_MAX    # noqa: E402 -- largest member count; checked against kEnsembleMax at a launch
+
+
+def score_ensemble(theta, phi, R, K, dflt, doc_a, word_a, doc_b, word_b, tol, max_blocks: int = 0):
+    """Ensemble scores of R members (csrc/hip/score_ensemble.hip; ``ops.reference.score_ensemble`` is the twin):
+    ``(score_a, score_b|None, key, flag, votes)`` as new device tensors.
+
+    ``theta`` [D, R, K] / ``phi`` [V, R, K] float64: the members' tables interleaved per row.  A side's score is
+    ``(((0.0 + s_0) + s_1) + ...) / R`` over the members' ``score_events`` scores s_r; ``key`` the lower side,
+    ``flag`` ``key < tol``, ``votes`` (uint8) the members whose own key is under ``tol``.  R = 1 is
+    ``score_events`` bit for bit.  Everything is checked on the host before the launch; ``n == 0`` launches
+    nothing.  ``max_blocks``: cap on the workgroups (tests: a small cap makes the grid-stride loop wrap)."""
+    import operator
+    R, K = operator.index(R), operator.index(K)
+    if not isinstance(max_blocks, int) or isinstance(max_blocks, bool) or max_blocks < 0:
+        raise ValueError(f"max_blocks must be a non-negative int, got {max_blocks!r}")
+    if not 1 <= R <= ENSEMBLE_MAX:
+        raise ValueError(f"score_ensemble: R must be in [1, {ENSEMBLE_MAX}], got {R}")
+    if K < 1:
+        raise ValueError(f"score_ensemble: K must be >= 1, got {K}")
+    for name, t in (("theta", theta), ("phi", phi)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 3:
+            raise ValueError(f"{name}: expected a [rows, R, K] tensor")
+        if t.dtype != torch.float64:
+            raise ValueError(f"{name}: expected torch.float64, got {t.dtype}")
+        if tuple(t.shape[1:]) != (R, K):
+            raise ValueError(f"{name}: row width {tuple(t.shape[1:])} != (R, K) = {(R, K)}")
+        if not t.is_cuda:
+            raise ValueError(f"{name}: must be a GPU tensor")
+        if not t.is_contiguous():
+            raise ValueError(f"{name}: must be contiguous")
+    if phi.device != theta.device:
+        raise ValueError(f"phi: on {phi.device}, expected {theta.device} (theta's device)")
+    if (doc_b is None) != (word_b is None):
+        raise ValueError("score_ensemble: doc_b and word_b go together")
+    if not isinstance(doc_a, torch.Tensor) or doc_a.dim() != 1:
+        raise ValueError("doc_a: expected a 1-D tensor")
+    dev = theta.device
+    D, V = theta.shape[0], phi.shape[0]
+    n = doc_a.numel()
+    if n >= 1 << 31:
+        raise ValueError(f"score_ensemble: {n} events (n < 2^31)")
+    two = doc_b is not None
+    ptr = []
+    for name, idx in (("doc_a", doc_a), ("word_a", word_a), ("doc_b", doc_b), ("word_b", word_b)):
+        if idx is None:
+            ptr.append(0)
+            continue
+        if not isinstance(idx, torch.Tensor) or idx.dtype != torch.int32:
+            raise ValueError(f"{name}: expected an int32 tensor")
+        if idx.device != dev:
+            raise ValueError(f"{name}: on {idx.device}, expected {dev}")
+        if tuple(idx.shape) != (n,):
+            raise ValueError(f"{name}: shape {tuple(idx.shape)} != {(n,)}")
+        if not idx.is_contiguous():
+            raise ValueError(f"{name}: must be contiguous")
+        ptr.append(idx.data_ptr())
+    # index bounds (host check before a gather kernel touches memory)
+    if n:
+        for name, idx, lim in (("doc_a", doc_a, D), ("word_a", word_a, V), ("doc_b", doc_b, D), ("word_b", word_b, V)):
+            if idx is not None and (int(idx.max()) >= lim or int(idx.min()) < -1):
+                raise ValueError(f"{name}: index out of range")
+    sa = torch.empty(n, dtype=torch.float64, device=dev)
+    sb = torch.empty(n, dtype=torch.float64, device=dev) if two else None
+    key = torch.empty(n, dtype=torch.float64, device=dev)
+    flag = torch.empty(n, dtype=torch.uint8, device=dev)
+    votes = torch.empty(n, dtype=torch.uint8, device=dev)
+    if n == 0:
+        return sa, sb, key, flag, votes
+    if lib().ensemble_max() != ENSEMBLE_MAX:
+        raise RuntimeError("score_ensemble: config.ENSEMBLE_MAX differs from the compiled kEnsembleMax")
+    lib().score_ensemble(theta.data_ptr(), phi.data_ptr(), R, K, float(dflt), *ptr, int(n), float(tol),
+                         sa.data_ptr(), sb.data_ptr() if two else 0, key.data_ptr(), flag.data_ptr(),
+                         votes.data_ptr(), int(max_blocks), _stream())
+    return sa, sb, key, flag, votes
+
+
 SELECT_TILE = 2048   # rows of one tile of the selection kernels (csrc/hip/kernels.h kSelectTile)
 
 

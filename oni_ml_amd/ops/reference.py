@@ -122,6 +122,34 @@ def score(theta, phi, K, dflt, doc_a, word_a, doc_b=None, word_b=None, tol=float
     return sa, sb, key, (key < tol).to(torch.uint8)
 
 
+def score_ensemble(theta, phi, R, K, dflt, doc_a, word_a, doc_b=None, word_b=None, tol=float("inf")):
+    """Torch twin of ``ops.hip.score_ensemble`` (csrc/hip/score_ensemble.hip) on any device, bit for bit:
+    ``(score_a, score_b|None, key, flag, votes)``.  ``theta`` [D, R, K] / ``phi`` [V, R, K]: the members'
+    tables interleaved per row.  Member r's side scores are ``score`` on its tables; a side's ensemble score is
+    ``(((0.0 + s_0) + s_1) + ... + s_{R-1}) / R``; ``votes`` counts the members whose own key is under ``tol``."""
+    if theta.dim() != 3 or phi.dim() != 3 or tuple(theta.shape[1:]) != (R, K) or tuple(phi.shape[1:]) != (R, K):
+        raise ValueError("score_ensemble: theta [D, R, K] and phi [V, R, K]")
+    if (doc_b is None) != (word_b is None):
+        raise ValueError("score_ensemble: doc_b and word_b go together")
+    n = doc_a.numel()
+    dev = doc_a.device
+    two = doc_b is not None
+    sum_a = torch.zeros(n, dtype=torch.float64, device=dev)
+    sum_b = torch.zeros(n, dtype=torch.float64, device=dev) if two else None
+    votes = torch.zeros(n, dtype=torch.uint8, device=dev)
+    for r in range(R):
+        sa, sb, _, _ = score(theta[:, r], phi[:, r], K, dflt, doc_a, word_a, doc_b, word_b, tol)
+        sum_a = sum_a + sa
+        if two:
+            sum_b = sum_b + sb
+        mk = torch.where(sa < sb, sa, sb) if two else sa       # the member's own key, a < b ? a : b as well
+        votes = votes + (mk < tol).to(torch.uint8)
+    ea = sum_a / float(R)
+    eb = sum_b / float(R) if two else None
+    key = torch.where(ea < eb, ea, eb) if two else ea      # the kernel's a < b ? a : b
+    return ea, eb, key, (key < tol).to(torch.uint8), votes
+
+
 def select_lowest(key, flag, limit, with_count: bool = False):
     """Torch twin of ``ops.hip.select_lowest`` (csrc/hip/select_lowest.hip) on any device: the row indices
     (int64, ascending) of the ``limit`` flagged rows that a stable ascending sort of their keys puts first, all

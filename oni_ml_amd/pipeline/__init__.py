@@ -8,6 +8,9 @@ def run(cfg, dist=None, device=None, log=print) -> dict:
     if cfg.host_report and dist is not None and dist.active:      # before any file or directory is made
         from ..config import HOST_REPORT_ONE_PROCESS
         raise ValueError(HOST_REPORT_ONE_PROCESS)
+    if cfg.ensemble > 1 and dist is not None and dist.active:
+        from ..config import ENSEMBLE_ONE_PROCESS
+        raise ValueError(ENSEMBLE_ONE_PROCESS)
     if cfg.dsource == "proxy":     # one process, no HDFS staging (pipeline/proxy.py raises for either)
         from .proxy import run as _run
         return _run(cfg, dist=dist, device=device, log=log)

@@ -28,6 +28,8 @@ class ModelTables:
     # to rows without decoding or hashing millions of word names
     word_keys: Optional[np.ndarray] = None
     key_space: Optional[object] = None
+    # --ensemble: (θ, φ) of the members 1 .. R-1, rows as in theta / phi (one corpus, one set of names)
+    members: Optional[list] = None
 
     def doc_index(self) -> dict:
         return {n: i for i, n in enumerate(self.doc_names)}      # later duplicates win (collectAsMap)
@@ -140,6 +142,197 @@ def load_model_tables(lpath: str) -> ModelTables:
     dn, th = lda_post.read_results(os.path.join(lpath, "doc_results.csv"))
     wn, ph = lda_post.read_results(os.path.join(lpath, "word_results.csv"))
     return ModelTables(dn, th, wn, ph)
+
+
+# ------------------------------------------------------------------ --ensemble
+# Member 0 is the run without --ensemble, in LPATH.  Member r >= 1 is the same corpus fitted from the seed
+# cfg.seed + r into <LPATH>/ensemble/m<r>/, a model directory of its own (final.*, likelihood.dat,
+# final_model.npz, then doc_results.csv / word_results.csv) with the completion marker MEMBER_DONE.
+MEMBER_DONE = ".done"
+
+
+def member_dir(lpath: str, r: int) -> str:
+    return os.path.join(lpath, "ensemble", f"m{r}")
+
+
+def member_fit_key(cfg, r: int) -> dict:
+    """What a member's marker must agree with for the member to be kept on a resume."""
+    return dict(member=r, seed=cfg.seed + r, topics=cfg.topics, alpha_init=cfg.alpha, start=cfg.start,
+                compat=cfg.compat)
+
+
+def member_done(cfg, r: int) -> bool:
+    """The member has its marker, and the marker is of this run's seed, topic count, alpha, start and compat mode
+    (a resume with another --seed or --topics fits the member again instead of mixing two runs)."""
+    path = os.path.join(member_dir(cfg.lpath, r), MEMBER_DONE)
+    if not os.path.exists(path):
+        return False
+    try:
+        m = load_json(path)
+    except ValueError:
+        return False
+    return all(m.get(k) == v for k, v in member_fit_key(cfg, r).items())
+
+
+def members_to_fit(cfg) -> List[int]:
+    """The members r >= 1 this run has to fit: all of them, or on a resume those that are not ``member_done``."""
+    return [r for r in range(1, cfg.ensemble) if not (cfg.resume and member_done(cfg, r))]
+
+
+def run_lda_members(cfg, corpus: Corpus, fit: List[int], device=None, log=print) -> dict:
+    """Fit the members ``fit`` one after the other, each from scratch (they are deterministic by seed): only the
+    000 and final model files (lag 0), no word assignments.  Returns {r: (gamma, log_beta)}."""
+    import dataclasses
+    import shutil
+    out = {}
+    settings = dataclasses.replace(cfg.settings, lag=0)
+    pending = []      # a member's model files are formatted on its writer threads while the next member fits
+    try:
+        for r in fit:
+            mdir = member_dir(cfg.lpath, r)
+            shutil.rmtree(mdir, ignore_errors=True)
+            res = estimate(corpus, cfg.topics, cfg.alpha, settings, cfg.start, mdir, backend=cfg.backend,
+                           device=device, seed=cfg.seed + r, resume=False, write_word_assignments=False,
+                           verbose=False, defer_files=True)
+            stats = dict(member_fit_key(cfg, r), em_iterations=res.em_iterations,
+                         likelihood=res.likelihoods[-1][0] if res.likelihoods else None, alpha=res.alpha,
+                         seconds=res.seconds)
+            pending.append((mdir, stats, res.close_files))
+            out[r] = (res.gamma, res.log_beta)
+            res.engine = None
+            log(f"lda: ensemble member {r} (seed {cfg.seed + r}): {stats['em_iterations']} EM iterations, "
+                f"likelihood {stats['likelihood']}, {stats['seconds']:.3f}s")
+    finally:
+        err = None
+        for mdir, stats, close in pending:      # the marker only once the member's files are complete
+            try:
+                close()
+                save_json(os.path.join(mdir, MEMBER_DONE), stats)
+            except Exception as e:  # noqa: BLE001 -- the other members' writers are still drained
+                err = err or e
+        if err is not None:
+            raise err
+    return out
+
+
+def report_members(cfg, summary: dict):
+    """Per member the EM iterations, final likelihood, alpha and seconds, into ``summary["lda"]["members"]`` and
+    the "ensemble" entry of LPATH's lda_stats.json (member 0: this run's lda stage, or what an earlier run
+    recorded there)."""
+    path = os.path.join(cfg.lpath, "lda_stats.json")
+    stats = load_json(path) if os.path.exists(path) else {}
+    lda = summary.get("lda")
+    if lda is not None:
+        m0 = dict(member=0, seed=cfg.seed, em_iterations=lda.get("em_iterations"), likelihood=lda.get("likelihood"),
+                  alpha=lda.get("alpha"), seconds=lda.get("seconds"))
+    elif stats.get("ensemble"):
+        m0 = stats["ensemble"][0]
+    else:      # a plain run resumed with --ensemble: what its lda stage left in LPATH
+        lik = None
+        lp = os.path.join(cfg.lpath, "likelihood.dat")
+        if os.path.exists(lp):
+            with open(lp) as f:
+                lines = f.read().split("\n")
+            lines = [x for x in lines if x.strip()]
+            lik = float(lines[-1].split()[0]) if lines else None
+        m0 = dict(member=0, seed=cfg.seed, em_iterations=stats.get("em_iterations"), likelihood=lik,
+                  alpha=stats.get("alpha"), seconds=stats.get("seconds"))
+    keep = ("member", "seed", "em_iterations", "likelihood", "alpha", "seconds")
+    members = [m0] + [{k: m.get(k) for k in keep}
+                      for m in (load_json(os.path.join(member_dir(cfg.lpath, r), MEMBER_DONE))
+                                for r in range(1, cfg.ensemble))]
+    summary.setdefault("lda", {})["members"] = members
+    if stats:
+        stats["ensemble"] = members
+        with open(path + ".tmp", "w") as f:
+            json.dump(stats, f)
+        os.replace(path + ".tmp", path)      # never a torn lda_stats.json
+
+
+def export_members(cfg, doc_names, word_names, fitted: dict) -> list:
+    """lda_post for the members 1 .. R-1: doc_results.csv / word_results.csv into each member directory, through
+    the text round trip of ``run_export`` (``fitted``: what ``run_lda_members`` returned; a member fitted by an
+    earlier run is read from its directory).  Returns their (θ, φ)."""
+    from concurrent.futures import ThreadPoolExecutor
+
+    from ..models.lda.estimate import load_final
+
+    def one(r):
+        mdir = member_dir(cfg.lpath, r)
+        gamma, log_beta = fitted[r] if r in fitted else load_final(mdir)
+        th, ph, _ = lda_post.export(doc_names, gamma, word_names, log_beta, os.path.join(mdir, "doc_results.csv"),
+                                    os.path.join(mdir, "word_results.csv"), strict=cfg.strict, read_back=True)
+        return th, ph
+    # every member writes its own two files: a few at a time (the native formatters release the GIL)
+    with ThreadPoolExecutor(max(1, min(4, cfg.ensemble - 1))) as ex:
+        return list(ex.map(one, range(1, cfg.ensemble)))
+
+
+def load_members(cfg) -> list:
+    """(θ, φ) of the members 1 .. R-1 from their result files (a resumed run)."""
+    out = []
+    for r in range(1, cfg.ensemble):
+        t = load_model_tables(member_dir(cfg.lpath, r))
+        out.append((t.theta, t.phi))
+    return out
+
+
+def votes_hist(votes, order, R: int) -> dict:
+    """``{"ensemble_votes_hist": h}``, h[v] the number of written rows (``order``) that v members flagged on their
+    own; ``{}`` without votes (one model)."""
+    if votes is None:
+        return {}
+    v = votes.cpu().numpy()[np.asarray(order, np.int64)]
+    return dict(ensemble_votes_hist=np.bincount(v, minlength=R + 1).astype(np.int64).tolist())
+
+
+class Ensemble:
+    """The --ensemble part of a one-process pipeline (flow, dns, proxy alike); with ``cfg.ensemble == 1`` every
+    method does nothing.  ``post``: the name of the pipeline's scoring stage."""
+
+    def __init__(self, cfg, runner, post: str, device=None, log=print):
+        import shutil
+        self.cfg, self.R, self.post, self.device, self.log = cfg, runner, post, device, log
+        self.on = cfg.ensemble > 1
+        if not cfg.resume:      # a fresh run fits every member: nothing of an earlier, maybe larger, ensemble stays
+            shutil.rmtree(os.path.join(cfg.lpath, "ensemble"), ignore_errors=True)
+        self.fit = members_to_fit(cfg)      # the members 1 .. R-1 still to fit
+        self.fitted = {}                    # {r: (gamma, log_beta)} of the members fitted in this process
+        if self.fit and cfg.resume:         # a member fitted again: its tables and the scores are made again
+            runner.invalidate("lda_post", post)
+
+    def lda_ran(self, corpus: Corpus, summary: dict):
+        """Inside the lda stage, after member 0: the other members, so the lda marker means every member."""
+        if self.on:
+            self.fitted = run_lda_members(self.cfg, corpus, self.fit, device=self.device, log=self.log)
+            report_members(self.cfg, summary)
+
+    def lda_skipped(self, corpus: Optional[Corpus], summary: dict):
+        """The lda stage is complete (member 0 is): fit the members that are not, timed but without a marker of
+        their own (each member directory has one)."""
+        if self.fit:
+            if corpus is None:
+                corpus = load_corpus_files(self.cfg.lpath)[0]
+            with self.R.stage("lda_members", mark=False):
+                self.fitted = run_lda_members(self.cfg, corpus, self.fit, device=self.device, log=self.log)
+        if self.on:
+            report_members(self.cfg, summary)
+
+    def exported(self, tables: ModelTables, doc_names, word_names):
+        """Inside the lda_post stage: the members' result files, and their tables beside member 0's."""
+        if self.on:
+            tables.members = export_members(self.cfg, doc_names, word_names, self.fitted)
+
+    def loaded(self, tables: ModelTables):
+        """The lda_post stage is complete: the members' tables from their result files."""
+        if self.on:
+            tables.members = load_members(self.cfg)
+
+    def scored(self, res: dict, summary: dict):
+        """Inside the scoring stage: ensemble_votes_hist into the summary and the metrics."""
+        if "ensemble_votes_hist" in res:
+            summary["ensemble_votes_hist"] = res["ensemble_votes_hist"]
+            self.R.emit(dict(stage=self.post + "_detail", ensemble_votes_hist=res["ensemble_votes_hist"]))
 
 
 def strict_tables(mt: ModelTables, strict: bool = True) -> ModelTables:

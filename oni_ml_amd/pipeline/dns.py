@@ -34,6 +34,7 @@ def run(cfg, dist=None, device=None, log=print) -> dict:
     doc_names = word_names = None
     top = None
     pre_host = None      # dns_pre's name features: dns_post takes its raw rows' slice
+    ens = C.Ensemble(cfg, R, "dns_post", device, log)      # --ensemble; inert with one model
     need_pre = not (R.done("lda_pre") and R.done("dns_pre"))
     if rank == 0 and (need_pre or not R.done("dns_post")):
         with R.stage("load") as res:
@@ -101,10 +102,12 @@ def run(cfg, dist=None, device=None, log=print) -> dict:
                                                                                    if not isinstance(v, list)}))
             summary["lda"] = dict(em_iterations=lres.em_iterations, timing=getattr(lres, "timing", {}), seconds=lres.seconds, alpha=lres.alpha,
                                   likelihood=lres.likelihoods[-1][0] if lres.likelihoods else None)
+            ens.lda_ran(corpus, summary)     # the lda marker is written once every member is done
         gamma, log_beta = lres.gamma, lres.log_beta
     else:
         R.skip("lda")
         gamma = log_beta = None
+        ens.lda_skipped(corpus, summary)     # member 0 is complete: the members that are not
     if rank != 0:
         R.finish_deferred()
         return summary
@@ -118,9 +121,11 @@ def run(cfg, dist=None, device=None, log=print) -> dict:
                 gamma, log_beta = load_final(cfg.lpath)
             with R.stage("lda_post"):
                 tables = C.run_export(cfg, doc_names, gamma, word_names, log_beta, read_back=True)
+                ens.exported(tables, doc_names, word_names)
         else:
             R.skip("lda_post")
             tables = C.load_model_tables(cfg.lpath)
+            ens.loaded(tables)
 
         if not R.done("dns_post"):
             with R.stage("dns_post") as res:
@@ -129,6 +134,7 @@ def run(cfg, dist=None, device=None, log=print) -> dict:
                 summary["below_tol"] = res.get("below_tol")
                 if cfg.host_report:
                     summary["hosts"], summary["host_sides_skipped"] = res.get("hosts"), res.get("host_sides_skipped")
+                ens.scored(res, summary)
         else:
             R.skip("dns_post")
     except BaseException:
@@ -169,8 +175,8 @@ def score_dns(cfg, tab: FD.DnsTable, top, tables: C.ModelTables, device, log=pri
     K = tables.K
     if cfg.strict and K != 20:
         raise ValueError("compat=strict scores over exactly 20 topics (dns_post_lda.scala:316)")
-    model = S.TopicModel.build(th, ph, S.default_value("dns", K, cfg.strict), device)
-    sc, _, key, flag = S.score(model, didx, widx, None, None, cfg.tol)
+    model = S.build_model(tables, th, ph, S.default_value("dns", K, cfg.strict), device)
+    sc, _, key, flag, votes = S.score_votes(model, didx, widx, None, None, cfg.tol)
     limit = cfg.max_results if cfg.max_results > 0 else None      # MAXRESULTS: the `limit` lowest scores only
     if limit is None:
         order = S.rank_flagged(key, flag)
@@ -212,7 +218,7 @@ def score_dns(cfg, tab: FD.DnsTable, top, tables: C.ModelTables, device, log=pri
     native.lib().write_rows(out, None, cols, threads=cfg.threads, n=n)
     log(f"dns_post: {C.flagged_text(n, below, limit, 'queries', cfg.tol)} written to {out}")
     hosts = C.write_host_report(cfg, tables, didx, sc, None, None, row_cols, log=log) if cfg.host_report else {}
-    return dict(flagged=n, below_tol=below, events=int(feat.word_key.numel()), **hosts)
+    return dict(flagged=n, below_tol=below, events=int(feat.word_key.numel()), **hosts, **C.votes_hist(votes, order, cfg.ensemble))
 
 
 def synthetic_dns_corpus(events: int = 2_000_000, seed: int = 0, device=None, strict: bool = True, threads: int = 8,

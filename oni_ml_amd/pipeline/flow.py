@@ -50,6 +50,7 @@ def run(cfg, dist=None, device=None, log=print) -> dict:
     summary = {}
     ft = feat = ws = built = None
     doc_names = word_names = None
+    ens = C.Ensemble(cfg, R, "flow_post", device, log)      # --ensemble; inert with one model
 
     # ------------------------------------------------------------------ pre
     need_pre = not (R.done("lda_pre") and R.done("flow_pre"))
@@ -123,10 +124,12 @@ def run(cfg, dist=None, device=None, log=print) -> dict:
                                                                                    if not isinstance(v, list)}))
             summary["lda"] = dict(em_iterations=lres.em_iterations, timing=getattr(lres, "timing", {}), seconds=lres.seconds, alpha=lres.alpha,
                                   likelihood=lres.likelihoods[-1][0] if lres.likelihoods else None)
+            ens.lda_ran(corpus, summary)     # the lda marker is written once every member is done
         gamma, log_beta = lres.gamma, lres.log_beta
     else:
         R.skip("lda")
         gamma = log_beta = None
+        ens.lda_skipped(corpus, summary)     # member 0 is complete: the members that are not
     if rank != 0:
         R.finish_deferred()
         return summary
@@ -157,9 +160,11 @@ def run(cfg, dist=None, device=None, log=print) -> dict:
                     tables = C.run_export(cfg, doc_names, gamma, word_names, log_beta, read_back=True)
                 if built is not None and ws is not None and not cfg.strict:
                     tables.word_keys, tables.key_space = np.asarray(built.word_keys), ws
+                ens.exported(tables, doc_names, word_names)
         else:
             R.skip("lda_post")
             tables = C.load_model_tables(cfg.lpath)
+            ens.loaded(tables)
 
         # ------------------------------------------------------------ flow_post
         if not R.done("flow_post"):
@@ -175,6 +180,7 @@ def run(cfg, dist=None, device=None, log=print) -> dict:
                 summary["below_tol"] = res.get("below_tol")
                 if cfg.host_report:
                     summary["hosts"], summary["host_sides_skipped"] = res.get("hosts"), res.get("host_sides_skipped")
+                ens.scored(res, summary)
         else:
             R.skip("flow_post")
     except BaseException:
@@ -237,9 +243,9 @@ def score_flow(cfg, ft: FF.FlowTable, tables: C.ModelTables, device, log=print, 
     K = tables.K
     if cfg.strict and K != 20:
         raise ValueError("compat=strict scores over exactly 20 topics (flow_post_lda.scala:232)")
-    model = S.TopicModel.build(th, ph, S.default_value("flow", K, cfg.strict), device)
+    model = S.build_model(tables, th, ph, S.default_value("flow", K, cfg.strict), device)
     d_src, d_dst = SG.gather(didx, feat.sip), SG.gather(didx, feat.dip)
-    sa, sb, key, flag = S.score(model, d_src, w_src, d_dst, w_dst, cfg.tol)
+    sa, sb, key, flag, votes = S.score_votes(model, d_src, w_src, d_dst, w_dst, cfg.tol)
     qs = S.key_quantiles(key)
     limit = cfg.max_results if cfg.max_results > 0 else None      # MAXRESULTS: the `limit` lowest scores only
     if limit is None:
@@ -289,7 +295,7 @@ def score_flow(cfg, ft: FF.FlowTable, tables: C.ModelTables, device, log=print, 
     native.lib().write_rows(out, None, cols, threads=cfg.threads, n=n)
     log(f"flow_post: {C.flagged_text(n, below, limit, 'events', cfg.tol)} written to {out}")
     hosts = C.write_host_report(cfg, tables, d_src, sa, d_dst, sb, row_cols, log=log) if cfg.host_report else {}
-    return dict(flagged=n, below_tol=below, events=int(feat.time.numel()), **qs, **hosts)
+    return dict(flagged=n, below_tol=below, events=int(feat.time.numel()), **qs, **hosts, **C.votes_hist(votes, order, cfg.ensemble))
 
 
 def synthetic_flow_corpus(events: int = 1_000_000, seed: int = 0, workdir: Optional[str] = None, device=None,

@@ -35,6 +35,7 @@ def run(cfg, dist=None, device=None, log=print) -> dict:
     doc_names = word_names = None
     top = None
     pre_host = None      # proxy_pre's cut-independent features: proxy_post reuses them
+    ens = C.Ensemble(cfg, R, "proxy_post", device, log)      # --ensemble; inert with one model
     need_pre = not (R.done("lda_pre") and R.done("proxy_pre"))
     if need_pre or not R.done("proxy_post"):
         with R.stage("load") as res:
@@ -88,10 +89,12 @@ def run(cfg, dist=None, device=None, log=print) -> dict:
             summary["lda"] = dict(em_iterations=lres.em_iterations, timing=getattr(lres, "timing", {}),
                                   seconds=lres.seconds, alpha=lres.alpha,
                                   likelihood=lres.likelihoods[-1][0] if lres.likelihoods else None)
+            ens.lda_ran(corpus, summary)     # the lda marker is written once every member is done
         gamma, log_beta = lres.gamma, lres.log_beta
     else:
         R.skip("lda")
         gamma = log_beta = None
+        ens.lda_skipped(corpus, summary)     # member 0 is complete: the members that are not
     try:
         if not R.done("lda_post"):
             if doc_names is None:
@@ -101,9 +104,11 @@ def run(cfg, dist=None, device=None, log=print) -> dict:
                 gamma, log_beta = load_final(cfg.lpath)
             with R.stage("lda_post"):
                 tables = C.run_export(cfg, doc_names, gamma, word_names, log_beta, read_back=True)
+                ens.exported(tables, doc_names, word_names)
         else:
             R.skip("lda_post")
             tables = C.load_model_tables(cfg.lpath)
+            ens.loaded(tables)
 
         if not R.done("proxy_post"):
             with R.stage("proxy_post") as res:
@@ -112,6 +117,7 @@ def run(cfg, dist=None, device=None, log=print) -> dict:
                 summary["below_tol"] = res.get("below_tol")
                 if cfg.host_report:
                     summary["hosts"], summary["host_sides_skipped"] = res.get("hosts"), res.get("host_sides_skipped")
+                ens.scored(res, summary)
         else:
             R.skip("proxy_post")
     except BaseException:
@@ -139,8 +145,8 @@ def score_proxy(cfg, tab: FP.ProxyTable, top, tables: C.ModelTables, device, log
     widx = SG.gather(torch.from_numpy(wrow).to(device), inv)
     didx = SG.gather(torch.from_numpy(drow).to(device), feat.ip)
     K = tables.K
-    model = S.TopicModel.build(th, ph, S.default_value("proxy", K, False), device)
-    sc, _, key, flag = S.score(model, didx, widx, None, None, cfg.tol)
+    model = S.build_model(tables, th, ph, S.default_value("proxy", K, False), device)
+    sc, _, key, flag, votes = S.score_votes(model, didx, widx, None, None, cfg.tol)
     limit = cfg.max_results if cfg.max_results > 0 else None      # MAXRESULTS: the `limit` lowest scores only
     if limit is None:
         order = S.rank_flagged(key, flag)
@@ -165,4 +171,4 @@ def score_proxy(cfg, tab: FP.ProxyTable, top, tables: C.ModelTables, device, log
     log(f"proxy_post: {C.flagged_text(n, below, limit, 'requests', cfg.tol)} written to {out}")
     hosts = (C.write_host_report(cfg, tables, didx, sc, None, None, row_cols, sep="\t", log=log)
              if cfg.host_report else {})
-    return dict(flagged=n, below_tol=below, events=int(feat.word_key.numel()), **hosts)
+    return dict(flagged=n, below_tol=below, events=int(feat.word_key.numel()), **hosts, **C.votes_hist(votes, order, cfg.ensemble))

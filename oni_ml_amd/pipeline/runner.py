@@ -89,6 +89,15 @@ class StageRunner:
     def done(self, name: str) -> bool:
         return self.resume and os.path.exists(os.path.join(self.mdir, name + ".done"))
 
+    def invalidate(self, *names: str):
+        """Drop the completion markers of these stages: a resumed run does them again."""
+        if self.rank == 0:
+            for name in names:
+                try:
+                    os.unlink(os.path.join(self.mdir, name + ".done"))
+                except FileNotFoundError:
+                    pass
+
     def info(self, name: str) -> dict:
         p = os.path.join(self.mdir, name + ".done")
         if os.path.exists(p):
@@ -106,8 +115,9 @@ class StageRunner:
             f.write(json.dumps(dict(rec, rank=self.rank)) + "\n")
 
     @contextmanager
-    def stage(self, name: str, **meta):
-        """Run a stage body; record time; write the completion marker with `result` dict entries."""
+    def stage(self, name: str, mark: bool = True, **meta):
+        """Run a stage body; record time; write the completion marker with `result` dict entries
+        (``mark=False``: timed and logged only, for work whose completion is recorded elsewhere)."""
         result = {}
         range_push(name)
         if self.sync:
@@ -139,7 +149,8 @@ class StageRunner:
             if self.rank == 0:
                 self.log(f"[stage {name}] {dt:.3f}s (files pending)")
             return
-        self._mark(name, rec)
+        if mark:
+            self._mark(name, rec)
         if self.rank == 0:
             self.log(f"[stage {name}] {dt:.3f}s")
 

@@ -35,6 +35,36 @@ class TopicModel:
         return TopicModel(th, ph, K, float(default))
 
 
+@dataclass
+class EnsembleModel:
+    """R members fitted on one corpus from different seeds (``--ensemble R``): their θ / φ interleaved per row,
+    so a side's R member rows are one contiguous run.  ``score`` gives the mean of the members' scores,
+    ``score_votes`` also how many members would have flagged each event on their own."""
+    theta: torch.Tensor            # [D, R, K] f64
+    phi: torch.Tensor              # [V, R, K] f64
+    R: int
+    K: int
+    default: float
+
+    @staticmethod
+    def build(members: Sequence, default: float, device, K: Optional[int] = None) -> "EnsembleModel":
+        """``members``: (θ [D, K'], φ [V, K']) host arrays of every member, member 0 first."""
+        K = int(members[0][0].shape[1] if K is None else K)
+        th = np.ascontiguousarray(np.stack([np.asarray(t, np.float64)[:, :K] for t, _ in members], axis=1))
+        ph = np.ascontiguousarray(np.stack([np.asarray(p, np.float64)[:, :K] for _, p in members], axis=1))
+        return EnsembleModel(torch.from_numpy(th).to(device), torch.from_numpy(ph).to(device), len(members), K,
+                             float(default))
+
+
+def build_model(tables, th, ph, default: float, device):
+    """The scorers' model of ``tables`` (pipeline/common.py ModelTables): a TopicModel, or with ``tables.members``
+    the EnsembleModel of member 0 (``th`` / ``ph``, as ``tables.compact`` returned them) and the others."""
+    members = getattr(tables, "members", None)
+    if members:
+        return EnsembleModel.build([(th, ph)] + list(members), default, device)
+    return TopicModel.build(th, ph, default, device)
+
+
 def default_value(source: str, K: int, strict: bool) -> float:
     """Miss vector: flow 0.05 x 20, dns 0.1 x 20 in the reference (sums 1.0 and 2.0); 1/K when fixed."""
     if strict:
@@ -42,8 +72,24 @@ def default_value(source: str, K: int, strict: bool) -> float:
     return 1.0 / K
 
 
-def score(model: TopicModel, doc_a, word_a, doc_b=None, word_b=None, tol: float = float("inf")):
-    """Returns (score_a, score_b|None, key, flag) device tensors."""
+def score_votes(model, doc_a, word_a, doc_b=None, word_b=None, tol: float = float("inf")):
+    """``score`` and, as a fifth value, the votes: for an EnsembleModel uint8 [n], the members whose own key is
+    under ``tol``; None for one model."""
+    if isinstance(model, EnsembleModel):
+        i32 = lambda t: None if t is None else t.to(torch.int32).contiguous()      # noqa: E731
+        if model.theta.device.type == "cuda":
+            from ..ops.hip import score_ensemble as fn
+        else:
+            from ..ops.reference import score_ensemble as fn
+        return fn(model.theta, model.phi, model.R, model.K, model.default, i32(doc_a), i32(word_a), i32(doc_b),
+                  i32(word_b), tol)
+    return tuple(score(model, doc_a, word_a, doc_b, word_b, tol)) + (None,)
+
+
+def score(model, doc_a, word_a, doc_b=None, word_b=None, tol: float = float("inf")):
+    """Returns (score_a, score_b|None, key, flag) device tensors, for either model kind."""
+    if isinstance(model, EnsembleModel):
+        return tuple(score_votes(model, doc_a, word_a, doc_b, word_b, tol))[:4]
     dev = model.theta.device
     if dev.type == "cuda":
         from ..ops import hip as H
