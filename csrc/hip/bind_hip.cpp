@@ -235,6 +235,21 @@ PYBIND11_MODULE(_onihip, m) {
     oni::launch_flow_words(a, S(stream));
   });
 
+  m.def("csc_part_tile", []() { return oni::kCscPartTile; });
+  m.def("csc_docs", [](u perm, u doc_ptr, int D, int nnz, u csc_ent, u csc_doc, u stream) {
+    oni::launch_csc_docs(P<const long long>(perm), P<const int>(doc_ptr), D, nnz, P<int>(csc_ent), P<int>(csc_doc),
+                         S(stream));
+  });
+  m.def("csc_partition", [](u csc_ent, u csc_doc, u word_ptr, u late, int nnz, int V, int D, int n_early, int n_late,
+                            u ce_early, u ce_late, u wp_early, u wp_late, u tile_sum, u before, u et_row, u et_s0,
+                            u et_w, u et_base, int umax, u stream) {
+    oni::CscPartArgs a{P<const int>(csc_ent), P<const int>(csc_doc), P<const int>(word_ptr), P<const uint8_t>(late),
+                       nnz, V, D, n_early, n_late, P<int>(ce_early), P<int>(ce_late), P<int>(wp_early),
+                       P<int>(wp_late), P<int>(tile_sum), P<int>(before), P<int>(et_row), P<const int>(et_s0),
+                       P<const int>(et_w), P<const int>(et_base), umax};
+    oni::launch_csc_partition(a, S(stream));
+  });
+
   m.def("bin_columns", [](std::vector<u> values, std::vector<u> cuts, std::vector<int> ncuts, int64_t n,
                           u bins, u stream) {
     if (values.size() != cuts.size() || values.size() != ncuts.size())

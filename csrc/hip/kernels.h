@@ -330,4 +330,36 @@ void launch_flow_words(const FlowWordArgs& a, hipStream_t s);
 void launch_bin_columns(const double* const* values, const double* const* cuts, const int* ncuts,
                         int ncols, int64_t n, int8_t* bins, hipStream_t s);
 
+// ------------------------------------------------------- engine construction ---
+// csc_ent[s] = perm[s] (the stable sort's int64 permutation, narrowed) and csc_doc[s] = the document whose
+// [doc_ptr[d], doc_ptr[d + 1]) holds that entry (corpus_plan.hip).
+void launch_csc_docs(const long long* perm, const int* doc_ptr, int D, int nnz, int* csc_ent, int* csc_doc,
+                     hipStream_t s);
+
+// Early / late partition of the CSC (corpus_plan.hip): slots whose document has late[d] != 0 go to ce_late, the
+// others to ce_early, slot order kept; wp_late[w] = late slots ahead of word_ptr[w], wp_early[w] the others.
+constexpr int kCscPartTile = 2048;   // slots per workgroup: tile_sum holds ceil(nnz / kCscPartTile) ints
+struct CscPartArgs {
+  const int* csc_ent;    // [nnz]
+  const int* csc_doc;    // [nnz]
+  const int* word_ptr;   // [V + 1]
+  const uint8_t* late;   // [D]
+  int nnz, V, D;
+  int n_early, n_late;   // the two sides' slots (n_early + n_late = nnz), from the host plan: bounds of the lists
+  int* ce_early;         // [n_early]
+  int* ce_late;          // [n_late]
+  int* wp_early;         // [V + 1]
+  int* wp_late;          // [V + 1]
+  int* tile_sum;         // scratch [max(1, ceil(nnz / kCscPartTile))]
+  int* before;           // scratch [nnz + 1]: late slots ahead of each slot
+  // deferred final pass (nullptr: none): et_row[i] of late slot i = et_base[d] + min((entry - et_s0[d]) /
+  // et_w[d], umax - 1) with d the slot's document
+  int* et_row;           // [n_late]
+  const int* et_s0;      // [D]
+  const int* et_w;       // [D]
+  const int* et_base;    // [D]
+  int umax;
+};
+void launch_csc_partition(const CscPartArgs& a, hipStream_t s);
+
 }  // namespace oni

@@ -17,6 +17,7 @@
 
 #include "corpus_io.h"
 #include "dns.h"
+#include "engine_plan.h"
 #include "fmt.h"
 #include "lda_ref.h"
 #include "table.h"
@@ -869,6 +870,80 @@ PYBIND11_MODULE(_oninative, m) {
         return out;
       },
       py::arg("K"), py::arg("V"), py::arg("seed"), py::arg("threads") = 0);
+
+  // ------------------------------------------------------------ engine plan --
+  // The fp64 engine's host plans in one pass into one caller-provided (pinned) buffer: engine_plan.h.
+  m.def("engine_plan_bound", &engine_plan_bound, py::arg("D"), py::arg("V"), py::arg("nnz"), py::arg("team8_lo"),
+        py::arg("xcds"));
+  m.def(
+      "engine_plan",
+      [](py::array_t<int64_t, py::array::c_style> doc_ptr, py::array_t<int32_t, py::array::c_style> word_idx,
+         py::array_t<int64_t, py::array::c_style> counts, int64_t V, int KS, int U,
+         std::vector<std::tuple<int, int64_t, int64_t>> edges, int tiny_variant, int team8_variant, int64_t tiny,
+         int64_t heavy, int64_t light, double late_share, int suff_split, double stage_cap, int umax, int iso_m,
+         int xcds, bool defer_final, py::array_t<uint8_t, py::array::c_style> buf, int threads) {
+        if (doc_ptr.ndim() != 1 || word_idx.ndim() != 1 || counts.ndim() != 1 || buf.ndim() != 1 ||
+            doc_ptr.size() < 1 || word_idx.size() != counts.size())
+          throw std::invalid_argument("engine_plan: 1-D doc_ptr [D + 1], word_idx / counts [nnz], buf");
+        EnginePlanIn in;
+        in.doc_ptr = doc_ptr.data();
+        in.word_idx = word_idx.data();
+        in.counts = counts.data();
+        in.D = (int64_t)doc_ptr.size() - 1;
+        in.V = V;
+        in.nnz = (int64_t)word_idx.size();
+        in.KS = KS;
+        in.U = U;
+        for (const auto& e : edges) in.edges.push_back({std::get<0>(e), std::get<1>(e), std::get<2>(e)});
+        in.tiny_variant = tiny_variant;
+        in.team8_variant = team8_variant;
+        in.tiny = tiny;
+        in.heavy = heavy;
+        in.light = light;
+        in.late_share = late_share;
+        in.suff_split = suff_split;
+        in.stage_cap = stage_cap;
+        in.umax = umax;
+        in.iso_m = iso_m;
+        in.xcds = xcds;
+        in.defer_final = defer_final;
+        in.threads = std::min(resolve_threads(threads), 16);
+        void* dst = buf.mutable_data();
+        const int64_t cap = (int64_t)buf.size();
+        EnginePlanOut r;
+        {
+          py::gil_scoped_release rel;
+          r = engine_plan(in, dst, cap);
+        }
+        py::dict d, sec;
+        for (const auto& s : r.sections) sec[py::str(s.name)] = py::make_tuple(s.offset, s.count, s.elem);
+        d["sections"] = sec;
+        py::list bk;
+        for (const auto& b : r.buckets) bk.append(py::make_tuple(b.variant, b.offset, b.count));
+        d["buckets"] = bk;
+        d["bytes"] = r.bytes;
+        d["doc_len"] = to_np(r.doc_len);
+        d["word_len"] = to_np(r.word_len);
+        py::list sc;
+        for (int i = 0; i < 3; ++i) sc.append(py::make_tuple(r.suff_counts[i][0], r.suff_counts[i][1], r.suff_counts[i][2]));
+        d["suff_counts"] = sc;
+        d["split"] = r.split;
+        d["defer"] = r.defer;
+        d["late_docs"] = r.late_docs;
+        d["n_early"] = r.n_early;
+        d["n_late"] = r.n_late;
+        d["staged"] = r.staged;
+        d["n_tiles"] = r.n_tiles;
+        d["csum"] = r.csum;
+        py::dict ph;
+        for (const auto& x : r.phase_us) ph[py::str(x.first)] = x.second;
+        d["phase_us"] = ph;
+        return d;
+      },
+      py::arg("doc_ptr"), py::arg("word_idx"), py::arg("counts"), py::arg("V"), py::arg("KS"), py::arg("U"),
+      py::arg("edges"), py::arg("tiny_variant"), py::arg("team8_variant"), py::arg("tiny"), py::arg("heavy"),
+      py::arg("light"), py::arg("late_share"), py::arg("suff_split"), py::arg("stage_cap"), py::arg("umax"),
+      py::arg("iso_m"), py::arg("xcds"), py::arg("defer_final"), py::arg("buf"), py::arg("threads") = 0);
 
   // ---------------------------------------------------------------- lda-c --
   m.def("digamma", &ldac_digamma);

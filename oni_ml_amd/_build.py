@@ -160,7 +160,10 @@ def build_native(verbose=False, jobs=8) -> Path:
     cxx = os.environ.get("CXX", "g++")
     out = LIB / ("_oninative" + _ext_suffix())
     hdrs = sorted((CSRC / "native").glob("*.h"))
-    srcs = [s for s in sorted((CSRC / "native").glob("*.cpp")) if s.name not in ("lda_main.cpp", "selftest.cpp")]
+    # every .cpp of csrc/native (engine_plan.cpp, the fp64 engine's host planner, included) but the programs
+    # with a main of their own
+    srcs = [s for s in sorted((CSRC / "native").glob("*.cpp"))
+            if s.name not in ("lda_main.cpp", "selftest.cpp", "engine_plan_check.cpp")]
     bind = CSRC / "native" / "bind_native.cpp"
     if not bind.exists():
         return None

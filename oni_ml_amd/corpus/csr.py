@@ -120,6 +120,20 @@ class DeviceCorpus:
         )
 
     @staticmethod
+    def from_arrays(doc_ptr, word_idx, counts, word_ptr, num_docs: int, num_terms: int, doc_len, word_len) -> "DeviceCorpus":
+        """From the narrowed CSR arrays and the column pointer already on the device and the host length
+        copies (the native engine plan's, models/lda/em.py ``_init_gs64_native``): the CSC permutation is one
+        stable device sort of the int32 word ids, the entry list and every slot's document one csc_docs
+        launch -- no searchsorted, no segment ids, no read-back."""
+        from ..ops import hip as H
+        nnz = int(word_idx.numel())
+        _, perm = torch.sort(word_idx, stable=True)
+        ent, doc = H.csc_docs(perm, doc_ptr, nnz)
+        return DeviceCorpus(doc_ptr=doc_ptr, word_idx=word_idx, counts=counts, word_ptr=word_ptr, csc_ent=ent,
+                            csc_doc=doc, num_docs=int(num_docs), num_terms=int(num_terms), nnz=nnz,
+                            doc_len=doc_len, word_len=word_len)
+
+    @staticmethod
     def _build_device(c: Corpus, dev) -> "DeviceCorpus":
         """The CSC permutation on the GPU: one stable radix sort of the word ids (nnz entries), the
         column pointer from a searchsorted -- instead of a host argsort of nnz entries (the engine's

@@ -188,7 +188,7 @@ class LDAEngine:
                  streams: int = 4, local_shard: bool = False, split_docs: bool = True,
                  split_min: Optional[int] = 4096, use_graph: bool = True, precision: str = "fp64",
                  emulate_shards: int = 0, doc_offset: int = 0, cphi_gb: Optional[float] = None,
-                 suff_split: str = "auto", defer_final: bool = True):
+                 suff_split: str = "auto", defer_final: bool = True, engine_plan: str = "native"):
         """precision: "fp64" (the only engine: lda-c's double arithmetic; the hip backend runs the block
         Gauss-Seidel schedule of lda_gs64.hip and the gs_*.hip kernel families).
         emulate_shards (torch backend, one process): reduce the sufficient statistics as the N
@@ -205,7 +205,13 @@ class LDAEngine:
         defer_final (fp64 hip engine, K <= 32, U <= 32): with the early / late split, the longest-document
         launch leaves its chunks' final-sweep E instead of writing its c.phi rows, and the late pass
         recomputes them (bitwise the same rows, computed by the whole GPU instead of the one CU every EM
-        iteration waits for); False: the launch writes them itself (A/B runs)."""
+        iteration waits for); False: the launch writes them itself (A/B runs).
+        engine_plan (fp64 hip engine): "native" -- where eligible (``_plan_native``) the construction plans come
+        from the native one-pass planner and one upload (``_init_gs64_native``); "python": the numpy / torch
+        planners everywhere (A/B runs, tests).  Both give the same arrays."""
+        if engine_plan not in ("native", "python"):
+            raise ValueError(f"engine_plan must be native | python, got {engine_plan!r}")
+        self.engine_plan = engine_plan
         self.cphi_gb = cphi_gb
         self.defer_final = bool(defer_final)
         if suff_split not in ("auto", "off", "force"):
@@ -401,11 +407,20 @@ class LDAEngine:
         here (beta, class_word, gamma, the per-entry c*phi rows, likelihood and alpha terms)."""
         from ...ops import hip as H
         self.KS = KS = H.padded_topics(self.K)
+        self._U = self.gs_updates()
+        self.plan_mode = "python"
+        if self._plan_native(KS):
+            # the last condition, looked at only here: an ineligible engine keeps its steps in their old order
+            self._cwin = self._cphi_windows(corpus, KS)
+            if self._cwin is None:
+                self.plan_mode = "native"
+                self._init_gs64_native(corpus, KS)
+                return
         self.dc = DeviceCorpus.build(corpus, self.device)
         dev, D, V, nnz = self.device, self.D, self.V, corpus.nnz
-        self._U = self.gs_updates()
         f64 = torch.float64
-        self._cwin = self._cphi_windows(corpus, KS)
+        if "_cwin" not in self.__dict__:
+            self._cwin = self._cphi_windows(corpus, KS)
         if self._cwin is None:
             self.gs_plan = H.GSPlan(self.dc.doc_len, KS, self._U, dev)
             self._split_sums(self.gs_plan, corpus)
@@ -416,10 +431,24 @@ class LDAEngine:
                 w["gp"] = H.GSPlan(self.dc.doc_len, KS, self._U, dev, doc_range=(w["d0"], w["d1"]))
                 self._split_sums(w["gp"], corpus)
             rows = max(w["e1"] - w["e0"] for w in self._cwin)
-        # one zero pad row past the vocabulary: gs_smallw's constant-offset row loads may read past row V - 1
-        self.beta = torch.zeros(V + 1, KS, dtype=f64, device=dev)[:V]
+        self._alloc_state(rows)
         self._stages = self._build_stages(corpus, KS)
         self._csums = self._build_chunk_sums(corpus, KS)
+        self.suff_plan = H.SuffPlan(self.dc.word_len, dev)
+        self._suff_part = torch.zeros(max(self.suff_plan.n_blocks, 1), 2 + KS, dtype=f64, device=dev)
+        self._suff_split = None
+        if self._cwin is not None:
+            self._build_window_suff()
+        elif self.suff_split != "off":
+            self._suff_split = self._build_suff_split()
+
+    def _alloc_state(self, rows: int):
+        """The engine's state buffers, streams and events: everything whose size the corpus alone fixes
+        (``rows``: the c.phi rows held at once), none of it a plan."""
+        from ...ops import hip as H
+        dev, D, V, KS, f64 = self.device, self.D, self.V, self.KS, torch.float64
+        # one zero pad row past the vocabulary: gs_smallw's constant-offset row loads may read past row V - 1
+        self.beta = torch.zeros(V + 1, KS, dtype=f64, device=dev)[:V]
         self.cw = torch.zeros(V, KS, dtype=f64, device=dev)
         self.gamma = torch.zeros(D, KS, dtype=f64, device=dev)
         # one pad row past the last entry: the suff-stats kernel's paired row loads (KS > 32) may read into it
@@ -436,8 +465,6 @@ class LDAEngine:
         self._distributed = self.dist is not None and self.dist.active
         self._cw_local = torch.zeros_like(self.cw) if self._distributed else self.cw
         self._red_local = torch.zeros_like(self._red) if self._distributed else self._red
-        self.suff_plan = H.SuffPlan(self.dc.word_len, dev)
-        self._suff_part = torch.zeros(max(self.suff_plan.n_blocks, 1), 2 + KS, dtype=f64, device=dev)
         self._done_count = torch.zeros(1, dtype=torch.int32, device=dev)
         self._alpha_dummy = torch.zeros(1, dtype=f64, device=dev)
         self._ct_fresh = False
@@ -453,11 +480,111 @@ class LDAEngine:
         self._fgraphs, self._fgraph_key = {}, None
         self._out_host = torch.zeros(self._ctlhist.numel(), dtype=f64).pin_memory()
         self._pushed = None
+
+    LATE_SHARE_MAX = 0.6   # no early / late suff-stats when the late bucket holds more of the entries than this
+
+    def _plan_native(self, KS: int) -> bool:
+        """``engine_plan="native"`` (default): the plans of the headline path -- a GPU, KS <= 32, U <= GS_LDS_UMAX,
+        no split documents, no c.phi windows -- come from one native pass and one upload
+        (``_init_gs64_native``); every other configuration, and "python", keeps the Python planners.
+        (``_cwin`` counts once ``_init_gs64`` has worked the windows out.)"""
+        from ...ops import hip as H
+        return (self.engine_plan == "native" and self.device.type == "cuda" and KS <= 32 and self._U <= H.GS_LDS_UMAX
+                and H.split_spec(KS)["min"] == 0 and getattr(self, "_cwin", None) is None)
+
+    def _stage_cap_bytes(self, KS: int) -> float:
+        """The staged rows' budget in bytes as ``_build_stages`` applies it (0: no staged rows)."""
+        gb = _stage_budget_gb(knobs.get("ONI_GS_STAGE", "4"))
+        return 0.0 if (KS > 32 or gb <= 0 or self._U > 32) else gb * 2**30
+
+    def host_plan(self, corpus: Corpus, KS: int, take=None) -> dict:
+        """The native planner's result for this engine's settings (ops/native.py ``engine_plan``), with the
+        thresholds (``th``) and the buffer (``buf``) added.  ``take(nbytes)`` returns the 256-byte-aligned uint8
+        array to plan into (None: a new numpy array)."""
+        from ...ops import hip as H, native
+        th = H.engine_plan_thresholds(KS, self._U)
+        lo8 = [lo for var, lo, _ in th["edges"] if var == H.GS_TEAM8]
+        bound = native.engine_plan_bound(corpus.num_docs, corpus.num_terms, corpus.nnz, lo8[0] if lo8 else 0, th["xcds"])
+        if take is None:
+            raw = np.empty(bound + 256, np.uint8)
+            a = (-raw.ctypes.data) % 256
+            buf = raw[a:a + bound]
+        else:
+            buf = take(bound)
+        p = native.engine_plan(corpus.doc_ptr, corpus.word_idx, corpus.counts, corpus.num_terms, KS, self._U, buf,
+                               late_share=self.LATE_SHARE_MAX, suff_split=self.suff_split,
+                               stage_cap=self._stage_cap_bytes(KS), defer_final=self.defer_final, **th)
+        p["buf"], p["th"] = buf, th
+        return p
+
+    def _init_gs64_native(self, corpus: Corpus, KS: int):
+        """``_init_gs64`` on the headline path: the state buffers' fills are queued first, the native planner
+        (csrc/native/engine_plan.cpp) writes every plan into one pooled pinned buffer while they run, one
+        asynchronous copy uploads it, and GSPlan / SuffPlan / GSStage / DeviceCorpus / the chunk sums / the
+        early-late split are views of that one device allocation; the CSC is one device sort plus the csc_docs
+        and csc_partition launches (csrc/hip/corpus_plan.hip).  No device-to-host read-back, no pageable
+        upload; the one host wait is for the upload's event at the end, before the pinned buffer goes back
+        to its pool.  Array for array what the Python planners build (tests/test_engine_plan*.py)."""
+        from ...ops import hip as H
+        dev, V, nnz, f64 = self.device, self.V, corpus.nnz, torch.float64
+        if nnz >= 2**31 - 1:
+            raise ValueError("nnz exceeds int32 offsets; shard the corpus")
+        self._alloc_state(nnz)
+        pinned = []
+
+        def take(nbytes):                     # whole MiB, so that the pool reuses the buffer for the next engine
+            pinned.extend(_PINNED.take((-(-nbytes // 2**20) * 2**20,), torch.uint8))
+            return pinned[1]
+
+        p = self.host_plan(corpus, KS, take=take)
+        th = p["th"]
+        self.plan_phase_us = dict(p["phase_us"])      # the planner's own phases (scripts/setup_profile.py)
+        arena = torch.empty(int(p["bytes"]), dtype=torch.uint8, device=dev)
+        arena.copy_(pinned[0][:arena.numel()], non_blocking=True)
+        uploaded = torch.cuda.Event()
+        uploaded.record()
+        sec = p["sections"]
+
+        def view(name, dtype):
+            off, n, el = sec[name]
+            return arena[off:off + n * el].view(dtype)
+
+        i32 = torch.int32
+        self.dc = DeviceCorpus.from_arrays(view("doc_ptr", i32), view("word_idx", i32), view("counts", torch.float32),
+                                           view("word_ptr", i32), self.D, V, p["doc_len"], p["word_len"])
+        plan = [(int(var), arena[off:off + 4 * n].view(i32)) for var, off, n in p["buckets"]]
+        self.gs_plan = H.GSPlan.from_arrays(KS, plan, th["tiny"])
+        team8 = [o for var, o in plan if var == H.GS_TEAM8]
+        self._stages, self._csums = {}, {}
+        if p["staged"]:
+            self._stages[id(team8[0])] = H.GSStage.from_arrays(
+                KS, p["n_tiles"], view("stage_tile_ent", i32), view("stage_tile_cnt", i32),
+                view("stage_off", torch.int64), dev)
+        if p["csum"]:
+            self._csums[id(team8[0])] = view("csum", f64).view(team8[0].numel(), H.GS_LDS_UMAX)
+        sc = p["suff_counts"]
+        self.suff_plan = H.SuffPlan.from_arrays(view("suff_order", i32), *sc[0])
+        need = max(self.suff_plan.n_blocks, 1)
         self._suff_split = None
-        if self._cwin is not None:
-            self._build_window_suff()
-        elif self.suff_split != "off":
-            self._suff_split = self._build_suff_split()
+        if p["split"]:
+            planE = H.SuffPlan.from_arrays(view("suff_order_early", i32), *sc[1])
+            planL = H.SuffPlan.from_arrays(view("suff_order_late", i32), *sc[2])
+            need = max(need, planE.n_blocks, planL.n_blocks)
+            tabs = (view("et_s0", i32), view("et_w", i32), view("et_base", i32)) if p["defer"] else None
+            part = H.csc_partition(self.dc.csc_ent, self.dc.csc_doc, self.dc.word_ptr, view("late_mask", torch.uint8),
+                                   p["n_early"], p["n_late"], et_tables=tabs)
+            ss = dict(wpE=part["wpE"], ceE=part["ceE"], planE=planE, wpL=part["wpL"], ceL=part["ceL"], planL=planL,
+                      cw_early=torch.zeros_like(self.cw), late_docs=int(p["late_docs"]))
+            if p["defer"]:
+                order = plan[0][1]
+                ss["et_order"] = id(order)
+                ss["et"] = torch.zeros(order.numel() * H.GS_LDS_UMAX * KS, dtype=f64, device=dev)
+                ss["et_row"] = part["et_row"]
+            self._suff_split = ss
+        self._suff_part = torch.zeros(need, 2 + KS, dtype=f64, device=dev)
+        self._plan_arena = arena
+        # the copy has left the pinned buffer: it goes back to the pool when this frame drops its array
+        uploaded.synchronize()
 
     @staticmethod
     def _split_sums(gp, corpus: Corpus) -> None:
@@ -582,7 +709,8 @@ class LDAEngine:
             o = self._order_host(gp.plan[key][1])
             late = o[o >= 0].astype(np.int64)
         force = self.suff_split == "force"
-        if late.size == 0 or (not force and dc.doc_len[late].sum() > 0.6 * max(1, int(dc.doc_len.sum()))):
+        if late.size == 0 or (not force and
+                              dc.doc_len[late].sum() > self.LATE_SHARE_MAX * max(1, int(dc.doc_len.sum()))):
             return None
         mask = torch.zeros(self.D, dtype=torch.bool, device=dev)
         mask[torch.from_numpy(late).to(dev)] = True

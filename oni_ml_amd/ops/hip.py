@@ -136,6 +136,16 @@ class SuffPlan:
         self.order = torch.from_numpy(order).to(device)
         self.n_blocks = int(lib().suff_fused_blocks(self.n_heavy, self.n_medium, self.n_light))
 
+    @classmethod
+    def from_arrays(cls, order, n_heavy: int, n_medium: int, n_light: int) -> "SuffPlan":
+        """A whole-vocabulary plan from an order already on the device (the native engine plan's)."""
+        self = cls.__new__(cls)
+        self.covers_all = True
+        self.n_heavy, self.n_medium, self.n_light = int(n_heavy), int(n_medium), int(n_light)
+        self.order = order
+        self.n_blocks = int(lib().suff_fused_blocks(self.n_heavy, self.n_medium, self.n_light))
+        return self
+
 
 def _scalar_slice(scalars, D, dev):
     if scalars is None:
@@ -605,6 +615,15 @@ class GSStage:
         self.stage_off = torch.from_numpy(off).to(device)
         self.buf = torch.zeros(max(nt, 1) * per * 2, dtype=torch.float64, device=device)
 
+    @classmethod
+    def from_arrays(cls, KS: int, n_tiles: int, tile_ent, tile_cnt, stage_off, device) -> "GSStage":
+        """Staged rows from tables already on the device (the native engine plan's)."""
+        self = cls.__new__(cls)
+        self.KS, self.n_tiles = int(KS), int(n_tiles)
+        self.tile_ent, self.tile_cnt, self.stage_off = tile_ent, tile_cnt, stage_off
+        self.buf = torch.zeros(max(self.n_tiles, 1) * (self.KS // 2) * 64 * 2, dtype=torch.float64, device=device)
+        return self
+
     @property
     def nbytes(self) -> int:
         return self.n_tiles * (self.KS // 2) * 64 * 16
@@ -795,6 +814,57 @@ def csc_subset(word_ptr, csc_ent, csc_doc, doc_mask):
     ce, before = SG.compact(csc_ent, keep)       # before[s]: kept slots ahead of slot s
     ptr = SG.gather(before, word_ptr)            # word w's kept slots start where its slots do
     return ptr.to(torch.int32), ce.contiguous(), (ptr[1:] - ptr[:-1]).cpu().numpy()
+
+
+def csc_docs(perm, doc_ptr, nnz: int):
+    """(csc_ent, csc_doc) int32 [nnz] from the int64 permutation of the stable word-id sort: the CSR entry of
+    every CSC slot and that entry's document (``doc_ptr`` int32 [D + 1] on the device), one launch."""
+    dev = perm.device
+    D = doc_ptr.numel() - 1
+    ent = torch.empty(nnz, dtype=torch.int32, device=dev)
+    doc = torch.empty(nnz, dtype=torch.int32, device=dev)
+    lib().csc_docs(_chk(perm, torch.int64, "perm", (nnz,), dev), _chk(doc_ptr, torch.int32, "doc_ptr", (D + 1,), dev),
+                   int(D), int(nnz), ent.data_ptr(), doc.data_ptr(), _stream())
+    return ent, doc
+
+
+def csc_partition(csc_ent, csc_doc, word_ptr, late, n_early: int, n_late: int, et_tables=None):
+    """The early / late CSC split in one partition pass (csrc/hip/corpus_plan.hip): the slots whose document has
+    ``late[d] != 0`` (uint8 [D], device) against the others, slot order kept -- what two ``csc_subset`` calls
+    return as (word_ptr, csc_ent), with the two sides' slot counts given by the caller (the host plan's
+    histogram; they bound the lists).  ``et_tables`` = (s0, W, base) int32 [D]: also ``gs_et_rows`` of the
+    late slots, et_row = base[doc] + min((entry - s0[doc]) // W[doc], GS_LDS_UMAX - 1).
+    Returns dict(ceE, ceL, wpE, wpL, et_row)."""
+    dev = csc_ent.device
+    nnz, V, D = csc_ent.numel(), word_ptr.numel() - 1, late.numel()
+    n_early, n_late = int(n_early), int(n_late)
+    if n_early < 0 or n_late < 0 or n_early + n_late != nnz:
+        raise ValueError(f"csc_partition: {n_early} early + {n_late} late slots, {nnz} in the CSC")
+    ce = torch.empty(nnz, dtype=torch.int32, device=dev)           # [early | late]
+    wp = torch.empty(2, V + 1, dtype=torch.int32, device=dev)
+    n_tiles = max(1, -(-nnz // int(lib().csc_part_tile())))
+    scratch = torch.empty(n_tiles + nnz + 1, dtype=torch.int32, device=dev)     # [tile sums | late slots ahead]
+    et_row, tabs = None, (0, 0, 0)
+    if et_tables is not None:
+        et_row = torch.empty(n_late, dtype=torch.int32, device=dev)
+        tabs = tuple(_chk(t, torch.int32, "et table", (D,), dev) for t in et_tables)
+    ceE, ceL = ce[:n_early], ce[n_early:]
+    lib().csc_partition(_chk(csc_ent, torch.int32, "csc_ent", (nnz,), dev),
+                        _chk(csc_doc, torch.int32, "csc_doc", (nnz,), dev),
+                        _chk(word_ptr, torch.int32, "word_ptr", (V + 1,), dev), _chk(late, torch.uint8, "late", (D,), dev),
+                        nnz, V, D, n_early, n_late, ceE.data_ptr(), ceL.data_ptr(), wp[0].data_ptr(), wp[1].data_ptr(),
+                        scratch.data_ptr(), scratch[n_tiles:].data_ptr(), 0 if et_row is None else et_row.data_ptr(),
+                        *tabs, GS_LDS_UMAX, _stream())
+    return dict(ceE=ceE, ceL=ceL, wpE=wp[0], wpL=wp[1], et_row=et_row)
+
+
+def engine_plan_thresholds(KS: int, U: int) -> dict:
+    """The thresholds of the native engine plan (ops/native.py ``engine_plan``), each from the Python
+    definition that owns it: GSPlan's edges and isolate_longest arguments, gs_tiny_max, SuffPlan's
+    heavy / light bounds, GS_LDS_UMAX."""
+    return dict(edges=GSPlan.EDGES_NARROW, tiny_variant=GS_TINY, team8_variant=GS_TEAM8,
+                tiny=min(gs_tiny_max(KS), int(U)), heavy=SuffPlan.HEAVY, light=SuffPlan.LIGHT, umax=GS_LDS_UMAX,
+                iso_m=GSPlan.ISO_M, xcds=GSPlan.XCDS)
 
 
 def suff_group_plan(lens, V: int):
@@ -1179,6 +1249,16 @@ class GSPlan:
     # KS <= 32: documents up to GS_SMALL_MAX words go to the 16-lanes-per-document kernel
     EDGES_NARROW = ((GS_TEAM8, 2048, None), (GS_TEAM4, 256, 2048), (GS_TEAM1, GS_SMALL_MAX, 256),
                     (GS_SMALL, None, GS_SMALL_MAX))
+    ISO_M, XCDS = 1, 8   # isolate_longest(o, m, xcds) of the team8 bucket at KS <= 32
+
+    @classmethod
+    def from_arrays(cls, KS: int, plan, tiny_max: int) -> "GSPlan":
+        """A plan without split documents from (variant, device order) pairs (the native engine plan's)."""
+        self = cls.__new__(cls)
+        self.KS, self.doc_range, self.split = int(KS), None, None
+        self.plan = list(plan)
+        self.tiny_max = int(tiny_max)
+        return self
 
     def __init__(self, lengths, KS: int, gs_updates: int, device, split_min: Optional[int] = None,
                  doc_range=None):
@@ -1218,7 +1298,7 @@ class GSPlan:
         self.plan = []
         # team8 at KS <= 32: the longest document first in a workgroup order that gives it an XCD of its own
         # under round-robin dispatch (isolate_longest, a speed hint)
-        iso = 1 if KS <= 32 else 0
+        iso = self.ISO_M if KS <= 32 else 0
         edges = self.EDGES_NARROW if KS <= 32 else self.EDGES
         if int(gs_updates) > 32:
             edges = self.wide_u_edges(int(gs_updates)) if KS > 32 else self.narrow_wide_u_edges(int(gs_updates))
@@ -1229,7 +1309,7 @@ class GSPlan:
                 continue
             o = order[m].copy()
             if var == GS_TEAM8 and iso > 0:
-                o = self.isolate_longest(o, min(iso, 8))
+                o = self.isolate_longest(o, min(iso, 8), self.XCDS)
             self.plan.append((var, torch.from_numpy(o).to(device)))
         m = Ls <= tiny
         if m.any():

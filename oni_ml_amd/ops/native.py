@@ -54,6 +54,28 @@ def background_thread_budget(share: int = 1) -> None:
     _LIB.set_default_threads(max(1, (int(knobs.threads(16)) - WRITER_RESERVE) // max(1, share)), True)
 
 
+def engine_plan_bound(D: int, V: int, nnz: int, team8_lo: int, xcds: int = 8) -> int:
+    """Upper bound of ``engine_plan``'s buffer bytes for a corpus of these sizes."""
+    return int(lib().engine_plan_bound(int(D), int(V), int(nnz), int(team8_lo), int(xcds)))
+
+
+def engine_plan(doc_ptr, word_idx, counts, V: int, KS: int, U: int, buf, *, edges, tiny_variant: int,
+                team8_variant: int, tiny: int, heavy: int, light: int, late_share: float, suff_split: str,
+                stage_cap: float, umax: int, iso_m: int, xcds: int, defer_final: bool, threads: int = 0) -> dict:
+    """The fp64 engine's host plans (csrc/native/engine_plan.cpp) from the host CSR (int64 ``doc_ptr``, int32
+    ``word_idx``, int64 ``counts``) into ``buf`` (uint8 numpy array, 256-byte aligned, at least
+    ``engine_plan_bound`` bytes), in one call.  Every threshold is an argument, passed by the caller from the
+    Python definition that owns it (ops/hip.py ``engine_plan_thresholds``).  ``edges``: (variant, lo, hi) per
+    bucket, None = the tiny bound / no upper edge.  Returns the section table {name: (byte offset, elements,
+    bytes per element)}, the buckets [(variant, byte offset, elements)], the host copies ``doc_len`` /
+    ``word_len`` and the plan's counts and flags."""
+    e = [(int(v), -1 if lo is None else int(lo), -1 if hi is None else int(hi)) for v, lo, hi in edges]
+    mode = {"off": 0, "auto": 1, "force": 2}[suff_split]
+    return lib().engine_plan(doc_ptr, word_idx, counts, int(V), int(KS), int(U), e, int(tiny_variant),
+                             int(team8_variant), int(tiny), int(heavy), int(light), float(late_share), mode,
+                             float(stage_cap), int(umax), int(iso_m), int(xcds), bool(defer_final), buf, int(threads))
+
+
 def available() -> bool:
     try:
         lib()

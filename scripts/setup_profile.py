@@ -4,7 +4,7 @@
 Builds the synthetic headline day, constructs the engine three times (the first loads code objects)
 and prints the wall time of each plus the top functions of the last under cProfile.
 
-  python scripts/setup_profile.py [--events 1000000] [--topics 20]
+  python scripts/setup_profile.py [--events 1000000] [--topics 20] [--plan native|python]
 """
 import argparse
 import cProfile
@@ -23,6 +23,8 @@ def main():
     ap.add_argument("--events", type=int, default=1_000_000)
     ap.add_argument("--topics", type=int, default=20)
     ap.add_argument("--top", type=int, default=40)
+    ap.add_argument("--plan", choices=["native", "python"], default=None,
+                    help="LDAEngine(engine_plan=...) of the constructions (default: the engine's, native)")
     a = ap.parse_args()
     import torch
     from oni_ml_amd.models.lda.em import LDAEngine
@@ -35,11 +37,16 @@ def main():
         t0 = time.perf_counter()
         if pr:
             pr.enable()
-        eng = LDAEngine(c, a.topics, LDASettings(), backend="hip", seed=1, precision="fp64")
+        eng = LDAEngine(c, a.topics, LDASettings(), backend="hip", seed=1, precision="fp64",
+                        **(dict(engine_plan=a.plan) if a.plan else {}))
         torch.cuda.synchronize()
         if pr:
             pr.disable()
-        print(f"construction {rep}: {1e3 * (time.perf_counter() - t0):.2f} ms", flush=True)
+        print(f"construction {rep} ({getattr(eng, 'plan_mode', 'python')} plan): "
+              f"{1e3 * (time.perf_counter() - t0):.2f} ms", flush=True)
+        if getattr(eng, "plan_phase_us", None):
+            print("  host planner, us: " + ", ".join(f"{k} {v:.0f}" for k, v in eng.plan_phase_us.items())
+                  + f" (sum {sum(eng.plan_phase_us.values()):.0f})", flush=True)
         del eng
     for key in ("cumulative", "tottime"):
         st = io.StringIO()
