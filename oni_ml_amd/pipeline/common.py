@@ -1,4 +1,5 @@
-"""Stages shared by the flow and DNS pipelines: corpus files, LDA, model export, model reload."""
+"""Shared by the flow, DNS and proxy pipelines: corpus files, LDA, model export and reload, the ensemble, the
+scorers' tails (the stage sequence itself: pipeline/driver.py)."""
 from __future__ import annotations
 
 import json
@@ -427,6 +428,64 @@ def write_host_report(cfg, tables: ModelTables, doc_a, score_a, doc_b, score_b, 
     native.lib().write_rows(out, None, cols, sep=sep, threads=cfg.threads, n=int(hosts.size))
     log(f"{cfg.dsource}_post: {hosts.size} hosts with a score < {cfg.tol} written to {out}")
     return dict(hosts=int(hosts.size), host_sides_skipped=int(skipped))
+
+
+def one_sided_index(tables, ip_names, ip, unames, inv, device, ip_map=None):
+    """The one-sided scorers' (dns, proxy) index set-up: (θ, φ, θ row of every event, φ row of every event).
+    ``ip`` / ``inv``: every event's id into ``ip_names`` / ``unames``; ``ip_map``: the doc row of every ip id
+    when the caller has it (a prefix of it is used), else looked up by name."""
+    from ..ops import sortgroup as SG
+    if ip_map is not None:
+        m = np.asarray(ip_map, np.int64)[:len(ip_names)]
+    else:
+        di = tables.doc_index()
+        m = np.fromiter((di.get(n, -1) for n in ip_names), dtype=np.int64, count=len(ip_names))
+    # the rows these events reference: the whole tables (one process) or fetched from their ranks
+    th, ph, drow, wrow = tables.compact(m, tables.word_rows(unames))
+    widx = SG.gather(torch.from_numpy(wrow).to(device), inv)
+    didx = SG.gather(torch.from_numpy(drow).to(device), ip)
+    return th, ph, didx, widx
+
+
+def rank_results(cfg, key, flag):
+    """(order, below, limit): the events under TOL ascending by ``key`` -- with MAXRESULTS only the ``limit``
+    lowest -- their count under TOL, and the limit (None: none)."""
+    from ..score import scorer as S
+    limit = cfg.max_results if cfg.max_results > 0 else None
+    if limit is None:
+        order = S.rank_flagged(key, flag)
+        return order, int(order.size), None
+    order, below = S.rank_flagged_counted(key, flag, limit)
+    return order, below, limit
+
+
+def write_results(cfg, tables, what: str, ranked, key, row_cols, events: int, sides, votes, log=print, ctx=None,
+                  sep: str = ",", extra=None) -> dict:
+    """``<type>_results.csv`` from ``ranked`` (what ``rank_results`` returned) and the scorer's ``row_cols``, the
+    log line, and the scoring stage's result.  One process: the rows, then the host report (``sides``: the
+    ``doc_a, score_a, doc_b, score_b`` of ``write_host_report``) and the votes histogram.  Several ranks
+    (``ctx``): the ranks' rows merged into one ascending file (``shardio.merge_sorted_rows``, the sortByKey
+    shuffle), the counts summed.  ``extra``: further result entries."""
+    from ..ops import native
+    order, below, limit = ranked
+    n = int(order.size)
+    out = os.path.join(cfg.lpath, f"{cfg.dsource}_results.csv")
+    cols = row_cols(order)
+    if ctx is not None and ctx.active:
+        from ..ops import sortgroup as SG
+        from ..parallel import shardio as SIO
+        text, ends = native.lib().format_rows(None, cols, n=n, row_ends=True, threads=cfg.threads)
+        key_o = SG.gather(key, torch.from_numpy(order).to(key.device)).cpu().numpy()
+        total = SIO.merge_sorted_rows(ctx, key_o.astype(np.float64), text, ends, out, limit=limit)
+        below = ctx.allreduce_int(below)
+        log(f"{cfg.dsource}_post: {flagged_text(total, below, limit, what, cfg.tol)} written to {out} "
+            f"({n} from rank {ctx.rank})")
+        return dict(flagged=total, below_tol=below, rank_flagged=n, events=ctx.allreduce_int(events), **(extra or {}))
+    native.lib().write_rows(out, None, cols, sep=sep, threads=cfg.threads, n=n)
+    log(f"{cfg.dsource}_post: {flagged_text(n, below, limit, what, cfg.tol)} written to {out}")
+    hosts = write_host_report(cfg, tables, *sides, row_cols, sep=sep, log=log) if cfg.host_report else {}
+    return dict(flagged=n, below_tol=below, events=events, **(extra or {}), **hosts,
+                **votes_hist(votes, order, cfg.ensemble))
 
 
 def save_json(path: str, obj):

@@ -25,7 +25,7 @@ from ..ops import sortgroup as SG
 from ..score import scorer as S
 from . import common as C
 from . import prefetch
-from .runner import StageRunner
+from .driver import PipelineSpec, Pre, run_stages
 
 
 def _host_cuts(ft, which: str):
@@ -35,160 +35,51 @@ def _host_cuts(ft, which: str):
     return hc.get(which) if hc else None
 
 
-def _word_names(ws: FF.FlowWordSpace, keys: np.ndarray):
-    return ws.decode(keys)
+def _load(cfg, res, summary, log):
+    ft = prefetch.take(prefetch.flow_key(cfg))
+    res["prefetched"] = ft is not None
+    if ft is None:
+        ft = FF.load_flow(cfg.flow_path, cfg.feedback_path(), cfg.dupfactor, cfg.threads)
+    res.update(ft.stats())
+    summary["input"] = ft.stats()
+    return ft
+
+
+def _pre(cfg, ft, device, res, log):
+    # cuts: CUT, else those the input prefetch computed on the host, else the device ECDF
+    cuts = cfg.fixed_cuts()
+    feat = FF.featurize(ft, device, cuts=cuts if cuts is not None else _host_cuts(ft, "all"))
+    ws = FF.word_space_for(feat)
+    src, dst = FF.word_keys(feat, ws)
+    dwc = concat([count_pairs(feat.sip, src, feat.weight), count_pairs(feat.dip, dst, feat.weight)],
+                 merge=not cfg.strict)
+    C.save_json(os.path.join(cfg.lpath, "flow_cuts.json"),
+                dict(cuts={k: v.tolist() for k, v in feat.cuts.items()}, ports=ws.ports.tolist()))
+    res["pairs"] = dwc.n
+    log(f"cuts: time={feat.cuts['time'].tolist()} ibyt={feat.cuts['ibyt'].tolist()} "
+        f"ipkt={feat.cuts['ipkt'].tolist()}")
+    return Pre(dwc, ft.ip_names, ws.decode, keep=ws)
+
+
+def _post(cfg, ft, tables, device, log, pre):
+    ip_rows = None
+    if pre is not None:
+        # documents built in this process: ip dictionary id -> doc row without the name lookup, and (fixed,
+        # tables exported in this process) word key -> φ row without the names
+        ip_rows = C.doc_rows_of(pre.built.doc_keys, len(ft.ip_names))
+        if pre.exported and not cfg.strict:
+            tables.word_keys, tables.key_space = np.asarray(pre.built.word_keys), pre.keep
+    return score_flow(cfg, ft, tables, device, log, ip_rows=ip_rows)
+
+
+SPEC = PipelineSpec("flow", _load, _pre, _post, defer_post=True)
 
 
 def run(cfg, dist=None, device=None, log=print) -> dict:
     if dist is not None and dist.active:
         from .sharded import run_flow
         return run_flow(cfg, dist, device, log)
-    rank = 0 if dist is None else dist.rank
-    device = torch.device(device or ("cuda" if torch.cuda.is_available() else "cpu"))
-    R = StageRunner(cfg.lpath, resume=cfg.resume, rank=rank, log=log,
-                    sync=(torch.cuda.synchronize if device.type == "cuda" else None))
-    summary = {}
-    ft = feat = ws = built = None
-    doc_names = word_names = None
-    ens = C.Ensemble(cfg, R, "flow_post", device, log)      # --ensemble; inert with one model
-
-    # ------------------------------------------------------------------ pre
-    need_pre = not (R.done("lda_pre") and R.done("flow_pre"))
-    sharded = False     # several ranks: pipeline/sharded.py
-    if rank == 0 and (need_pre or not R.done("flow_post")) and not sharded:
-        with R.stage("load") as res:
-            ft = prefetch.take(prefetch.flow_key(cfg))
-            res["prefetched"] = ft is not None
-            if ft is None:
-                ft = FF.load_flow(cfg.flow_path, cfg.feedback_path(), cfg.dupfactor, cfg.threads)
-            res.update(ft.stats())
-            summary["input"] = ft.stats()
-    if need_pre:
-        if rank == 0:
-            with R.stage("flow_pre") as res:
-                # cuts: CUT, else those the input prefetch computed on the host, else the device ECDF
-                cuts = cfg.fixed_cuts()
-                feat = FF.featurize(ft, device, cuts=cuts if cuts is not None else _host_cuts(ft, "all"))
-                ws = FF.word_space_for(feat)
-                src, dst = FF.word_keys(feat, ws)
-                dwc = concat([count_pairs(feat.sip, src, feat.weight), count_pairs(feat.dip, dst, feat.weight)],
-                             merge=not cfg.strict)
-                C.save_json(os.path.join(cfg.lpath, "flow_cuts.json"),
-                            dict(cuts={k: v.tolist() for k, v in feat.cuts.items()}, ports=ws.ports.tolist()))
-                res["pairs"] = dwc.n
-                log(f"cuts: time={feat.cuts['time'].tolist()} ibyt={feat.cuts['ibyt'].tolist()} "
-                    f"ipkt={feat.cuts['ipkt'].tolist()}")
-            with R.stage("lda_pre") as res:
-                built = lda_pre(dwc)
-                ipn = ft.ip_names
-                doc_names = [ipn[i] for i in built.doc_keys.tolist()]
-                word_names = _word_names(ws, built.word_keys)
-                lp, b_, dn_, wn_ = cfg.lpath, built, doc_names, word_names
-
-                # host copies here, not on the writer thread (DocWordCounts.to_host)
-                dwc_h = dwc.to_host() if cfg.write_doc_wc else None
-
-                def write_files():
-                    if dwc_h is not None:
-                        from ..corpus.builder import write_doc_wc
-                        write_doc_wc(os.path.join(lp, "doc_wc.dat"), dwc_h, ipn, C.vocab_lookup(b_.word_keys, wn_))
-                    C.write_corpus_files(lp, b_, dn_, wn_)
-                # the text files are the stage contract, not an input of the in-memory lda stage: written
-                # on a thread while the GPU runs EM; the lda_pre marker waits for them (finish_deferred)
-                if True:   # text files on a thread beside the EM (profiles/r3_tuning_log.md: e2e 0.66 -> 0.53 s)
-                    res["_defer"] = C.background(write_files, "oni-lda-pre-writer")
-                else:
-                    write_files()
-                res.update(docs=built.corpus.num_docs, terms=built.corpus.num_terms, nnz=built.corpus.nnz)
-                summary["corpus"] = dict(docs=built.corpus.num_docs, terms=built.corpus.num_terms, nnz=built.corpus.nnz)
-    elif not sharded:
-        R.skip("flow_pre")
-        R.skip("lda_pre")
-
-    # ------------------------------------------------------------------ lda
-    corpus = built.corpus if built is not None else None
-    if not R.done("lda"):
-        if corpus is None and rank == 0:
-            corpus, doc_names, word_names = C.load_corpus_files(cfg.lpath)
-        if dist is not None and dist.world_size > 1 and not sharded:
-            corpus = dist.broadcast_corpus(corpus)
-        with R.stage("lda") as res:
-            lres = C.run_lda(cfg, corpus, dist=dist, device=device, log=log)
-            res["_defer"] = lres.close_files   # LAG / final model files: written while later stages run
-            res.update(getattr(lres, "timing", {}))
-            res.update(em_iterations=lres.em_iterations, likelihood=lres.likelihoods[-1][0] if lres.likelihoods else 0.0,
-                       alpha=lres.alpha)
-            m = lres.engine.metrics(lres.seconds, lres.em_iterations)
-            res.update({k: v for k, v in m.items() if not isinstance(v, list)})
-            R.emit(dict(stage="lda_detail", var_iter_hist=m["var_iter_hist"], **{k: v for k, v in m.items()
-                                                                                   if not isinstance(v, list)}))
-            summary["lda"] = dict(em_iterations=lres.em_iterations, timing=getattr(lres, "timing", {}), seconds=lres.seconds, alpha=lres.alpha,
-                                  likelihood=lres.likelihoods[-1][0] if lres.likelihoods else None)
-            ens.lda_ran(corpus, summary)     # the lda marker is written once every member is done
-        gamma, log_beta = lres.gamma, lres.log_beta
-    else:
-        R.skip("lda")
-        gamma = log_beta = None
-        ens.lda_skipped(corpus, summary)     # member 0 is complete: the members that are not
-    if rank != 0:
-        R.finish_deferred()
-        return summary
-    try:
-
-        # ------------------------------------------------------------- lda_post
-        if not R.done("lda_post"):
-            if doc_names is None:
-                _, doc_names, word_names = C.load_corpus_files(cfg.lpath)
-            if gamma is None:
-                from ..models.lda.estimate import load_final
-                gamma, log_beta = load_final(cfg.lpath)
-            with R.stage("lda_post") as res:
-                # deferred text: measured no e2e gain on the 1-day tables (tuning log); on from
-                # DEFER_POST_VALUES (2^26) values, where formatting ~1 G values (config 5) overlaps scoring
-                big = (len(doc_names) + len(word_names)) * int(gamma.shape[1]) >= C.DEFER_POST_VALUES
-                if big:
-                    # the result files are written on a thread while flow_post scores (its tables
-                    # are the text round trip of the same values); the lda_post marker waits for them
-                    from ..export import lda_post as LP
-                    th, ph, wn, join = LP.export_deferred(doc_names, gamma, word_names, log_beta,
-                                                          os.path.join(cfg.lpath, "doc_results.csv"),
-                                                          os.path.join(cfg.lpath, "word_results.csv"),
-                                                          strict=cfg.strict)
-                    tables = C.ModelTables(list(doc_names), th, wn, ph)
-                    res["_defer"] = join
-                else:
-                    tables = C.run_export(cfg, doc_names, gamma, word_names, log_beta, read_back=True)
-                if built is not None and ws is not None and not cfg.strict:
-                    tables.word_keys, tables.key_space = np.asarray(built.word_keys), ws
-                ens.exported(tables, doc_names, word_names)
-        else:
-            R.skip("lda_post")
-            tables = C.load_model_tables(cfg.lpath)
-            ens.loaded(tables)
-
-        # ------------------------------------------------------------ flow_post
-        if not R.done("flow_post"):
-            if ft is None:
-                # row-sharded pre stages: rank 0 reads the whole day for the scoring pass
-                ft = prefetch.take(prefetch.flow_key(cfg)) or FF.load_flow(cfg.flow_path, cfg.feedback_path(),
-                                                                          cfg.dupfactor, cfg.threads)
-            # documents built in this process: ip dictionary id -> doc row without the name lookup
-            ip_rows = C.doc_rows_of(built.doc_keys, len(ft.ip_names)) if built is not None else None
-            with R.stage("flow_post") as res:
-                res.update(score_flow(cfg, ft, tables, device, log, ip_rows=ip_rows))
-                summary["scored"] = res.get("flagged")
-                summary["below_tol"] = res.get("below_tol")
-                if cfg.host_report:
-                    summary["hosts"], summary["host_sides_skipped"] = res.get("hosts"), res.get("host_sides_skipped")
-                ens.scored(res, summary)
-        else:
-            R.skip("flow_post")
-    except BaseException:
-        R.finish_deferred(suppress=True)
-        raise
-    R.finish_deferred()
-    summary["stage_seconds"] = dict(R.times)
-    return summary
+    return run_stages(cfg, SPEC, device, log)
 
 
 def score_flow(cfg, ft: FF.FlowTable, tables: C.ModelTables, device, log=print, ctx=None, ip_rows=None) -> dict:
@@ -198,9 +89,8 @@ def score_flow(cfg, ft: FF.FlowTable, tables: C.ModelTables, device, log=print, 
     and the survivors of all ranks are merged into one ascending file (``shardio.merge_sorted_rows``,
     the sortByKey shuffle).  ``ip_rows``: doc row of every ip dictionary id of ``ft`` (-1: not a
     document) -- replaces the name lookup through ``tables.doc_index()``."""
-    from ..parallel import shardio as SIO
     multi = ctx is not None and ctx.active
-    cuts = cfg.fixed_cuts()          # fixed CUT cuts apply to both stages (flow_pre_lda.scala:95-98)
+    cuts = cfg.fixed_cuts()         # fixed CUT cuts apply to both stages (flow_pre_lda.scala:95-98)
     if cuts is None and not cfg.strict:
         saved = C.load_json(os.path.join(cfg.lpath, "flow_cuts.json"))
         cuts = {k: np.asarray(v, np.float64) for k, v in saved["cuts"].items()}
@@ -247,14 +137,7 @@ def score_flow(cfg, ft: FF.FlowTable, tables: C.ModelTables, device, log=print, 
     d_src, d_dst = SG.gather(didx, feat.sip), SG.gather(didx, feat.dip)
     sa, sb, key, flag, votes = S.score_votes(model, d_src, w_src, d_dst, w_dst, cfg.tol)
     qs = S.key_quantiles(key)
-    limit = cfg.max_results if cfg.max_results > 0 else None      # MAXRESULTS: the `limit` lowest scores only
-    if limit is None:
-        order = S.rank_flagged(key, flag)
-        below = int(order.size)
-    else:
-        order, below = S.rank_flagged_counted(key, flag, limit)
-    n = int(order.size)
-    out = os.path.join(cfg.lpath, "flow_results.csv")
+    ranked = C.rank_results(cfg, key, flag)
     # output columns: 27 raw + time + ibyt_bin + ipkt_bin + time_bin + word_port + ip_pair + src/dest word + scores
     def row_cols(order):
         """The 37 columns of the given events, in that order."""
@@ -281,21 +164,8 @@ def score_flow(cfg, ft: FF.FlowTable, tables: C.ModelTables, device, log=print, 
             ("java", sel(sa)),
             ("java", sel(sb)),
         ]
-    cols = row_cols(order)
-    from ..ops import native
-    if multi:
-        text, ends = native.lib().format_rows(None, cols, n=n, row_ends=True, threads=cfg.threads)
-        key_o = SG.gather(key, torch.from_numpy(order).to(device)).cpu().numpy()
-        total = SIO.merge_sorted_rows(ctx, key_o.astype(np.float64), text, ends, out, limit=limit)
-        below = ctx.allreduce_int(below)
-        log(f"flow_post: {C.flagged_text(total, below, limit, 'events', cfg.tol)} written to {out} "
-            f"({n} from rank {ctx.rank})")
-        return dict(flagged=total, below_tol=below, rank_flagged=n,
-                    events=ctx.allreduce_int(int(feat.time.numel())), **qs)
-    native.lib().write_rows(out, None, cols, threads=cfg.threads, n=n)
-    log(f"flow_post: {C.flagged_text(n, below, limit, 'events', cfg.tol)} written to {out}")
-    hosts = C.write_host_report(cfg, tables, d_src, sa, d_dst, sb, row_cols, log=log) if cfg.host_report else {}
-    return dict(flagged=n, below_tol=below, events=int(feat.time.numel()), **qs, **hosts, **C.votes_hist(votes, order, cfg.ensemble))
+    return C.write_results(cfg, tables, "events", ranked, key, row_cols, int(feat.time.numel()),
+                           (d_src, sa, d_dst, sb), votes, log, ctx=ctx, extra=qs)
 
 
 def synthetic_flow_corpus(events: int = 1_000_000, seed: int = 0, workdir: Optional[str] = None, device=None,

@@ -27,6 +27,7 @@ import torch
 
 from ..parallel import shardio as SIO
 from . import common as C
+from .driver import lda_stage
 from .runner import StageRunner
 
 
@@ -70,23 +71,6 @@ def write_doc_wc_sharded(ctx, path, sc, ip_names, word_names_of, threads=0):
     SIO.write_segments(ctx, path, segs)
 
 
-def _lda_stage(R, cfg, ctx, corpus, device, log, summary, local_shard, doc_offset=0):
-    with R.stage("lda") as res:
-        lres = C.run_lda(cfg, corpus, dist=ctx, device=device, log=log, local_shard=local_shard,
-                         doc_offset=doc_offset)
-        res["_defer"] = lres.close_files   # LAG / final model files: written while later stages run
-        res.update(getattr(lres, "timing", {}))
-        res.update(em_iterations=lres.em_iterations, likelihood=lres.likelihoods[-1][0] if lres.likelihoods else 0.0,
-                   alpha=lres.alpha)
-        m = lres.engine.metrics(lres.seconds, lres.em_iterations)
-        res.update({k: v for k, v in m.items() if not isinstance(v, list)})
-        R.emit(dict(stage="lda_detail", var_iter_hist=m["var_iter_hist"],
-                    **{k: v for k, v in m.items() if not isinstance(v, list)}))
-        summary["lda"] = dict(em_iterations=lres.em_iterations, timing=getattr(lres, "timing", {}), seconds=lres.seconds, alpha=lres.alpha,
-                              likelihood=lres.likelihoods[-1][0] if lres.likelihoods else None)
-    return lres
-
-
 def _files_state(cfg, ctx):
     """Resume: the corpus files on every rank, this rank's shard of them (the engine's own rule,
     ``dist.engine_bounds``: the engine that re-runs the lda stage splits the documents the same way)."""
@@ -98,8 +82,6 @@ def _files_state(cfg, ctx):
 
 def run_flow(cfg, ctx, device=None, log=print) -> dict:
     from ..corpus.sharded import build_sharded
-    from ..export import lda_post
-    from ..features import flow as FF
     from ..features import flow_dist as FD
     from .flow import score_flow
     device = torch.device(device or ("cuda" if torch.cuda.is_available() else "cpu"))
@@ -107,7 +89,6 @@ def run_flow(cfg, ctx, device=None, log=print) -> dict:
     summary = {}
     rank0 = ctx.rank == 0
     ft = sc = names = gmap = ws = None
-    lres = None
     need_pre = not (R.done("lda_pre") and R.done("flow_pre"))
     if need_pre or not R.done("flow_post"):
         with R.stage("load") as res:
@@ -134,29 +115,12 @@ def run_flow(cfg, ctx, device=None, log=print) -> dict:
     else:
         R.skip("flow_pre")
         R.skip("lda_pre")
-    try:
-        tables, ip_rows = _lda_and_export(R, cfg, ctx, sc, names, gmap,
-                                          (lambda k: ws.decode(k)) if ws is not None else None, device, log, summary)
-        # ------------------------------------------------------------ flow_post
-        if not R.done("flow_post"):
-            with R.stage("flow_post") as res:
-                res.update(score_flow(cfg, ft, tables, device, log if rank0 else (lambda *a, **k: None),
-                                      ctx=ctx, ip_rows=ip_rows))
-                summary["scored"] = res.get("flagged")
-                summary["below_tol"] = res.get("below_tol")
-        else:
-            R.skip("flow_post")
-    except BaseException:
-        R.finish_deferred(suppress=True)
-        raise
-    R.finish_deferred()
-    summary["stage_seconds"] = dict(R.times)
-    return summary
+    return _finish(R, cfg, ctx, sc, names, gmap, ws, device, log, summary, "flow_post",
+                   lambda tables, ip_rows, slog: score_flow(cfg, ft, tables, device, slog, ctx=ctx, ip_rows=ip_rows))
 
 
 def run_dns(cfg, ctx, device=None, log=print) -> dict:
     from ..corpus.sharded import build_sharded
-    from ..export import lda_post
     from ..features import dns as FD
     from ..features import dns_dist as FDD
     from .dns import score_dns
@@ -194,17 +158,23 @@ def run_dns(cfg, ctx, device=None, log=print) -> dict:
     else:
         R.skip("dns_pre")
         R.skip("lda_pre")
+    return _finish(R, cfg, ctx, sc, names, gmap, wsp, device, log, summary, "dns_post",
+                   lambda tables, ip_rows, slog: score_dns(cfg, tab, top, tables, device, slog, ctx=ctx, ip_map=ip_rows))
+
+
+def _finish(R, cfg, ctx, sc, names, gmap, wspace, device, log, summary, post, score):
+    """What follows lda_pre in both pipelines: lda, lda_post, the scoring stage ``post`` --
+    ``score(tables, ip_rows, log)``, logging on rank 0 only -- and the deferred writers."""
     try:
         tables, ip_rows = _lda_and_export(R, cfg, ctx, sc, names, gmap,
-                                          (lambda k: wsp.decode(k)) if wsp is not None else None, device, log, summary)
-        if not R.done("dns_post"):
-            with R.stage("dns_post") as res:
-                res.update(score_dns(cfg, tab, top, tables, device, log if rank0 else (lambda *a, **k: None),
-                                     ctx=ctx, ip_map=ip_rows))
+                                          wspace.decode if wspace is not None else None, device, log, summary)
+        if not R.done(post):
+            with R.stage(post) as res:
+                res.update(score(tables, ip_rows, log if ctx.rank == 0 else (lambda *a, **k: None)))
                 summary["scored"] = res.get("flagged")
                 summary["below_tol"] = res.get("below_tol")
         else:
-            R.skip("dns_post")
+            R.skip(post)
     except BaseException:
         R.finish_deferred(suppress=True)
         raise
@@ -225,11 +195,12 @@ def _lda_and_export(R, cfg, ctx, sc, names, gmap, decode, device, log, summary):
     gamma = log_beta = None
     if not R.done("lda"):
         if sc is not None:
-            lres = _lda_stage(R, cfg, ctx, sc.corpus, device, log, summary, True, sc.doc_range[0])
+            lres = lda_stage(R, cfg, sc.corpus, device, log, summary, dist=ctx, local_shard=True,
+                             doc_offset=sc.doc_range[0])
         else:
             corpus, all_docs, word_names, (d0, d1) = _files_state(cfg, ctx)
             doc_names = all_docs[d0:d1]
-            lres = _lda_stage(R, cfg, ctx, corpus, device, log, summary, False)
+            lres = lda_stage(R, cfg, corpus, device, log, summary, dist=ctx)
         gamma, log_beta = lres.gamma, lres.log_beta
     else:
         R.skip("lda")

@@ -379,6 +379,89 @@ def test_flow_post_paths_byte_identical(tmp_path, monkeypatch, compat):
     assert (d / "ml" / "flow_results.csv").read_bytes() == outs["plain"]["flow_results.csv"]
 
 
+_RESUME_DAYS = {}
+_RESUME_TOL = dict(flow=1e-3, dns=1e-2, proxy=1e-3)
+_UNTIMED_SKIP = {"metrics.jsonl", "run_summary.json", "lda_stats.json"}
+
+
+def _resume_day(which, tmp_path_factory):
+    """(cfg maker, LPATH of the fresh run, its files) of the small day ``which``, run once for the module."""
+    if which not in _RESUME_DAYS:
+        kind, compat = which.split("-")
+        root = tmp_path_factory.mktemp("resume_" + kind + compat)
+        if kind == "flow":
+            from oni_ml_amd.synth.flow import generate_flow_day
+            generate_flow_day(str(root / "in") + "/", events=1500, seed=11, n_internal=300, n_external=600)
+            paths = dict(flow_path=str(root / "in"))
+        elif kind == "dns":
+            from oni_ml_amd.synth.dns import generate_dns_day
+            g = generate_dns_day(str(root / "in"), events=2000, seed=3, files=3, n_names=800, n_clients=300)
+            paths = dict(dns_path=g["dns_path"], top1m=g["top1m"])
+        else:
+            from oni_ml_amd.synth.proxy import generate_proxy_day
+            g = generate_proxy_day(str(root / "in"), events=1500, seed=5, files=2)
+            paths = dict(proxy_path=g["proxy_path"], top1m=g["top1m"])
+
+        def make(lpath, **kw):
+            cfg = CFG.resolve("20160122", kind, tol=_RESUME_TOL[kind], conf_path=None, environ={}, lpath=str(lpath),
+                              backend="torch", threads=2, verbose=False, compat=compat, **paths, **kw)
+            cfg.settings = LDASettings(em_max_iter=1)
+            return cfg.validate()
+        s = run(make(root / "fresh"), device="cpu", log=lambda *a, **k: None)
+        assert s["scored"] > 100
+        _RESUME_DAYS[which] = (make, root, _lpath_files(root / "fresh"))
+    return _RESUME_DAYS[which]
+
+
+def _lpath_files(lp):
+    """relative path -> bytes of every file under LPATH but the timed records, .stages/ and dot-files."""
+    out = {}
+    for r, dirs, files in os.walk(lp):
+        dirs[:] = [d for d in dirs if not d.startswith(".")]
+        for f in files:
+            if f not in _UNTIMED_SKIP and not f.startswith("."):
+                p = os.path.join(r, f)
+                with open(p, "rb") as fh:
+                    out[os.path.relpath(p, lp)] = fh.read()
+    return out
+
+
+@pytest.mark.parametrize("boundary", ["lda_pre", "lda", "lda_post", "complete"])
+@pytest.mark.parametrize("which", ["flow-strict", "flow-fixed", "dns-strict", "proxy-fixed"])
+def test_resume_matrix_writes_the_fresh_run(which, boundary, tmp_path_factory):
+    """Every pipeline type resumed after lda_pre, lda, lda_post and from a complete run: the later stages'
+    markers and files removed, the resumed run skips exactly the finished stages and leaves every file under
+    LPATH with the bytes of the uninterrupted run."""
+    import re
+    import shutil
+    make, root, want = _resume_day(which, tmp_path_factory)
+    kind = which.split("-")[0]
+    post, results = f"{kind}_post", f"{kind}_results.csv"
+    lp = root / ("at_" + boundary)
+    shutil.copytree(root / "fresh", lp)
+    model = [f for f in os.listdir(lp) if f.startswith("final.") or re.match(r"\d{3}\.", f)] + ["likelihood.dat"]
+    tables = ["doc_results.csv", "word_results.csv"]
+    markers, files = {"lda_pre": (["lda", "lda_post", post], model + tables + [results]),
+                      "lda": (["lda_post", post], tables + [results]),
+                      "lda_post": ([post], [results]),
+                      "complete": ([], [])}[boundary]
+    if boundary == "lda_pre":
+        assert {"final.beta", "final.gamma", "final.other", "000.beta", "000.other"} <= set(model), model
+    for m in markers:
+        os.unlink(lp / ".stages" / f"{m}.done")
+    for f in files:
+        os.unlink(lp / f)
+    logs = []
+    run(make(lp, resume=True), device="cpu", log=logs.append)
+    skipped = re.findall(r"\[stage (\w+)\] already complete", "\n".join(str(x) for x in logs))
+    stages = [f"{kind}_pre", "lda_pre", "lda", "lda_post", post]
+    assert sorted(skipped) == sorted(s for s in stages if s not in markers), (skipped, markers)
+    got = _lpath_files(lp)
+    assert sorted(got) == sorted(want) and results in got
+    for f in want:
+        assert got[f] == want[f], f
+
+
 def test_bench_plain_run_and_dump_outputs(tmp_path):
     """bench.py on the CPU rehearsal path: a plain run reports the headline alone (no ml_ops legs: those are
     --full's), --steps sets the timed steps, and --dump-outputs writes the last timed step's arrays, the
