@@ -197,6 +197,22 @@ PYBIND11_MODULE(_onihip, m) {
     oni::launch_host_summary(a, max_blocks, S(stream));
   });
 
+  m.def("explain_max_fields", []() { return oni::kExplainMaxFields; });
+  m.def("group_rows_sum", [](u table, u order, u seg_start, u seg_end, u blk_off, int64_t G, int64_t B, int W,
+                             int block, u scratch, u out, int max_blocks, u stream) {
+    oni::GroupRowsArgs a{P<const double>(table),    P<const int>(order),     P<const int64_t>(seg_start),
+                         P<const int64_t>(seg_end), P<const int64_t>(blk_off), G, B, W, block,
+                         P<double>(scratch),        P<double>(out)};
+    oni::launch_group_rows_sum(a, max_blocks, S(stream));
+  });
+  m.def("explain_sides", [](u theta, u phi, u gsum, int R, int K, int F, double dflt, u doc, u word, u grow,
+                            int64_t n, u cond, u why, int max_blocks, u stream) {
+    oni::ExplainArgs a{P<const double>(theta), P<const double>(phi), P<const double>(gsum), R, K, F, dflt,
+                       P<const int>(doc),      P<const int>(word),   P<const int>(grow),    n,
+                       P<double>(cond),        P<uint8_t>(why)};
+    oni::launch_explain_sides(a, max_blocks, S(stream));
+  });
+
   m.def("string_entropy", [](u bytes, u offsets, int64_t n, u table, int64_t table_len, u out, int max_blocks,
                              u stream) {
     if (n < 0 || table_len < 2 || max_blocks < 0) throw std::runtime_error("string_entropy: bad sizes");

@@ -288,6 +288,46 @@ struct HostSummaryArgs {
 // max_blocks: cap on the workgroups per launch (0: 2048)
 void launch_host_summary(const HostSummaryArgs& a, int max_blocks, hipStream_t s);
 
+// --explain (explain.hip).  group_rows_sum: row g of `out` is the sum of the table rows
+// order[seg_start[g] .. seg_end[g]), column by column, in a fixed order: the segment is cut into blocks of
+// `block` members, every block is summed from 0.0 in member order, the block sums are added from 0.0 in
+// block order.  Plain rounded fp64 adds, no atomics.
+struct GroupRowsArgs {
+  const double* table;       // [V][W]
+  const int* order;          // [V] table rows, every value in [0, V) (checked on the host)
+  const int64_t* seg_start;  // [G] 0 <= seg_start <= seg_end <= V (checked on the host)
+  const int64_t* seg_end;    // [G]
+  const int64_t* blk_off;    // [G + 1] exclusive prefix sum of the segments' block counts ceil(len / block)
+  int64_t G;                 // segments, 1 <= G < 2^31
+  int64_t B;                 // blocks of all segments, blk_off[G], < 2^31
+  int W;                     // doubles of a row
+  int block;                 // members of a block, >= 1
+  double* scratch;           // [B][W] block sums of the segments of more than one block
+  double* out;               // [G][W]
+};
+// max_blocks: cap on the workgroups per launch (0: 4096)
+void launch_group_rows_sum(const GroupRowsArgs& a, int max_blocks, hipStream_t s);
+
+// explain_sides: per side the score s = theta[doc] . phi[word] as score_ensemble computes it, the same
+// expression m_f with the row grow[i][f] of `gsum` in place of the phi row, cond[i][f] = s / m_f and why[i]
+// the lowest f with the lowest non-NaN cond (255: none).  cond is NaN where word[i] < 0 or grow[i][f] < 0.
+constexpr int kExplainMaxFields = 8;
+struct ExplainArgs {
+  const double* theta;   // [D][R][K]
+  const double* phi;     // [V][R][K]
+  const double* gsum;    // [Gtot][R][K] group sums of phi rows
+  int R, K, F;           // 1 <= R <= kEnsembleMax, K >= 1, 1 <= F <= kExplainMaxFields
+  double dflt;           // value of the default vector of a side without a document
+  const int* doc;        // [n] theta row or -1
+  const int* word;       // [n] phi row or -1
+  const int* grow;       // [n][F] gsum row or -1
+  int64_t n;             // 0 <= n < 2^31
+  double* cond;          // [n][F]
+  uint8_t* why;          // [n]
+};
+// max_blocks: cap on the workgroups (0: 8192)
+void launch_explain_sides(const ExplainArgs& a, int max_blocks, hipStream_t s);
+
 // Byte entropy of every string of a batch (string_entropy.hip): out[i] = (t[n] - sum_b t[c_b]) / n over the
 // bytes [offsets[i], offsets[i + 1]) of `bytes`, t = table (c log2 c, host-built), 0 for n <= 1.
 struct StringEntropyArgs {

@@ -91,9 +91,11 @@ def _apply_lda_args(a, st):
 
 
 def clean_workdir(lpath: str):
-    """ml_ops.sh:53-54: remove stale *.dat,*.beta,*.gamma,*.other,*.pkl; keep *.csv (analyst feedback)."""
+    """ml_ops.sh:53-54: remove stale *.dat,*.beta,*.gamma,*.other,*.pkl; keep *.csv (analyst feedback) -- except
+    what an earlier --explain run left, ``<type>_explain.csv`` and ``word_fields.npz``: a fresh run removes them
+    with or without the flag, since their lines would not describe this run's results file."""
     for pat in ("*.dat", "*.beta", "*.gamma", "*.other", "*.pkl", "checkpoint.npz", "final_model.npz",
-                "final_gamma.rank*.npz"):
+                "final_gamma.rank*.npz", "word_fields.npz", "*_explain.csv"):
         for f in glob.glob(os.path.join(lpath, pat)):
             os.unlink(f)
     shutil.rmtree(os.path.join(lpath, ".stages"), ignore_errors=True)
@@ -114,6 +116,9 @@ def cmd_ml_ops(argv):
     ap.add_argument("--ensemble", type=int, default=None, metavar="R",
                     help="score by the mean of R models fitted from the seeds --seed, --seed + 1, ... (1 <= R <= 64; "
                          "default 1 or ENSEMBLE; one process only)")
+    ap.add_argument("--explain", action="store_true", default=None,
+                    help="also write <type>_explain.csv: per written side the field of its word that makes it rare "
+                         "and the conditional probability of every field (or EXPLAIN=1; one process only)")
     ap.add_argument("--conf", default=knobs.get("ONI_CONF", "/etc/duxbay.conf"))
     ap.add_argument("--lpath")
     ap.add_argument("--flow-path")
@@ -165,11 +170,14 @@ def cmd_ml_ops(argv):
                            compat=a.compat, seed=a.seed, start=a.start, resume=a.resume, threads=a.threads,
                            write_doc_wc=a.keep_doc_wc, word_assignments=a.word_assignments,
                            rank_gamma=a.rank_gamma, verbose=not a.quiet, cuts=a.cuts, hdfs=a.hdfs or None,
-                           hadoop=a.hadoop, host_report=a.host_report, ensemble=a.ensemble)
+                           hadoop=a.hadoop, host_report=a.host_report, ensemble=a.ensemble, explain=a.explain)
     # --ensemble / ENSEMBLE (the site file and the environment set it too): refused here, before anything is
     # written and before a process group is asked for
-    CFG.RunConfig.check_ensemble(resolve(1).ensemble, a.start, a.gpus, a.hdfs,
-                                 int(os.environ.get("WORLD_SIZE", "1")))
+    first = resolve(1)
+    CFG.RunConfig.check_ensemble(first.ensemble, a.start, a.gpus, a.hdfs, int(os.environ.get("WORLD_SIZE", "1")))
+    # --explain / EXPLAIN likewise
+    if first.explain and (a.gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1 or a.hdfs):
+        raise ValueError(CFG.EXPLAIN_ONE_PROCESS)
     # one process, fresh run: the day's inputs are read on a thread while torch imports
     # (pipeline/prefetch.py); the load stage takes the result
     from .pipeline import prefetch

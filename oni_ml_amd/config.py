@@ -26,7 +26,7 @@ from typing import Dict, List, Optional
 from .models.lda.settings import LDASettings
 
 ENV_KEYS = ("FLOW_PATH", "DNS_PATH", "PROXY_PATH", "HPATH", "LPATH", "LUSER", "TOL", "DUPFACTOR", "KRB_AUTH", "NODES",
-            "UINODE", "RPATH", "LDAPATH", "SPK_EXEC", "SPK_EXEC_MEM", "TOP1M", "CUT", "MAXRESULTS", "ENSEMBLE")
+            "UINODE", "RPATH", "LDAPATH", "SPK_EXEC", "SPK_EXEC_MEM", "TOP1M", "CUT", "MAXRESULTS", "ENSEMBLE", "EXPLAIN")
 
 # proxy has no multi-rank, sharded or HDFS-staged form
 PROXY_ONE_PROCESS = "proxy runs on one process: launch it without torchrun, with --gpus 1 and without --hdfs"
@@ -37,6 +37,15 @@ HOST_REPORT_ONE_PROCESS = "--host-report runs on one process: launch it without 
 # the ensemble's members are fitted and scored by one process: no multi-rank, sharded or HDFS-staged form
 ENSEMBLE_ONE_PROCESS = "--ensemble runs on one process: launch it without torchrun, with --gpus 1 and without --hdfs"
 ENSEMBLE_MAX = 64
+
+# the explain file is made from one process's scored sides and its vocabulary's keys: no multi-rank, sharded or
+# HDFS-staged form
+EXPLAIN_ONE_PROCESS = "--explain runs on one process: launch it without torchrun, with --gpus 1 and without --hdfs"
+EXPLAIN_MAX_FIELDS = 8     # explained fields of a word space (csrc/hip/kernels.h kExplainMaxFields)
+# members of one block of a group sum (ops.hip / ops.reference group_rows_sum): a group's rows are summed block by
+# block in member order, then the block sums in block order; the value is part of the result's bits
+GROUP_BLOCK = 256
+WORD_FIELDS = "word_fields.npz"      # <LPATH>/word_fields.npz: the vocabulary's keys and fields, under --explain
 
 _VAR = re.compile(r"\$\{([A-Za-z_][A-Za-z0-9_]*)\}|\$([A-Za-z_][A-Za-z0-9_]*)")
 
@@ -92,6 +101,8 @@ class RunConfig:
                                           # the seeds seed, seed + 1, ...; 1: one model, as ever
     host_report: int = 0                  # --host-report: also write <type>_hosts.csv; 0: off, -1: every host with a
                                           # side under TOL, N >= 1: the N hosts with the lowest scores
+    explain: bool = False                 # --explain / EXPLAIN: also write <type>_explain.csv, per written side the
+                                          # field of its word that makes it rare
     lpath: str = ""                       # local working dir (reference: ${LUSER}/ml/${FDATE})
     hpath: str = ""                       # HDFS dir in the reference; unused unless set (optional copy target)
     flow_path: str = ""
@@ -164,6 +175,8 @@ class RunConfig:
             raise ValueError(f"--host-report must be 0 (off), -1 (every flagged host) or >= 1, got {self.host_report}")
         if self.host_report and (self.gpus > 1 or self.hdfs):
             raise ValueError(HOST_REPORT_ONE_PROCESS)
+        if self.explain and (self.gpus > 1 or self.hdfs):
+            raise ValueError(EXPLAIN_ONE_PROCESS)
         self.check_ensemble(self.ensemble, self.start, self.gpus, self.hdfs)
         return self
 
@@ -227,6 +240,8 @@ def _apply(cfg: RunConfig, layer: Dict[str, object]):
         cfg.max_results = int(layer["MAXRESULTS"])
     if "ENSEMBLE" in layer and layer["ENSEMBLE"] not in ("", None):
         cfg.ensemble = int(layer["ENSEMBLE"])
+    if "EXPLAIN" in layer and layer["EXPLAIN"] not in ("", None):
+        cfg.explain = str(layer["EXPLAIN"]).strip().lower() not in ("0", "false", "no", "off")
     if "DUPFACTOR" in layer and layer["DUPFACTOR"] not in ("", None):
         cfg.dupfactor = int(layer["DUPFACTOR"])
     if "CUT" in layer and isinstance(layer["CUT"], str) and layer["CUT"].strip():

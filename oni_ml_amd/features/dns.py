@@ -131,6 +131,12 @@ class DnsWordSpace:
         return native.lib().radix_word_names(np.asarray(keys, np.int64), [int(r) for r in self.radix],
                                              list(self.qpairs))
 
+    def fields(self):
+        """(name, radix, explained) of every digit of a key, most significant first (--explain); ``top``'s radix
+        is what remains of the key (top_domain is 0, 1 or 2)."""
+        return ([("top", 3, True)] + [(k, int(r), True) for k, r in zip(self.ORDER, self.radix)]
+                + [("qpair", max(1, len(self.qpairs)), True)])
+
     def decode_py(self, keys: np.ndarray) -> List[str]:
         k = np.asarray(keys, np.int64)
         nq = max(1, len(self.qpairs))

@@ -64,6 +64,12 @@ class FlowWordSpace:
         return native.lib().flow_word_names(np.asarray(self.ports, np.float64), self.NT, self.NB, self.NP,
                                             np.asarray(keys, np.int64))
 
+    def fields(self):
+        """(name, radix, explained) of every digit of a key, most significant first (--explain).  ``side``, the
+        "-1_" prefix, is a property of the port rule and not an observation: it is never left open."""
+        return [("port", max(1, int(self.ports.size)), True), ("time", self.NT, True), ("ibyt", self.NB, True),
+                ("ipkt", self.NP, True), ("side", 2, False)]
+
     def decode_py(self, keys: np.ndarray) -> List[str]:
         k = np.asarray(keys, np.int64)
         prefix = k % 2

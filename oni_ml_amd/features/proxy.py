@@ -169,6 +169,12 @@ class ProxyWordSpace:
         self.methods, self.ctypes, self.resps = list(feat.methods), list(feat.ctypes), list(feat.resps)
         self.n_abin = len(feat.cuts["agent"]) + 1
 
+    def fields(self):
+        """(name, radix, explained) of every digit of a key, most significant first (--explain)."""
+        return [("top", TOP_RADIX, True), ("hour", HOUR_RADIX, True), ("method", max(1, len(self.methods)), True),
+                ("ebin", len(ENTROPY_CUTS) + 1, True), ("ctype", max(1, len(self.ctypes)), True),
+                ("abin", self.n_abin, True), ("resp", max(1, len(self.resps)), True)]
+
     def decode(self, keys: np.ndarray) -> List[str]:
         """In Python, column-wise as ``DnsWordSpace.decode_py``: method and content-type names sit inside the word."""
         k = np.asarray(keys, np.int64)

@@ -17,6 +17,8 @@ from typing import Optional
 
 import torch
 
+from .. import config as _CFG      # GROUP_BLOCK, EXPLAIN_MAX_FIELDS: read at every call, one constant for kernel and twin
+
 _LIB = None
 _ERR = None
 
@@ -453,6 +455,152 @@ def host_summary(doc_a, score_a, doc_b, score_b, num_docs, tol, max_blocks: int 
     out = (u32(events), u32(flagged), min_score, torch.where(w == 0xFFFFFFFF, torch.full_like(w, -1), w),
            host[0] & 0xFFFFFFFF)
     return out + (tuple(host[1:]),) if stats else out
+
+
+def _max_blocks(max_blocks):
+    if not isinstance(max_blocks, int) or isinstance(max_blocks, bool) or max_blocks < 0:
+        raise ValueError(f"max_blocks must be a non-negative int, got {max_blocks!r}")
+    return max_blocks
+
+
+def _table3(name, t, R, K, dev=None):
+    if not isinstance(t, torch.Tensor) or t.dim() != 3:
+        raise ValueError(f"{name}: expected a [rows, R, K] tensor")
+    if t.dtype != torch.float64:
+        raise ValueError(f"{name}: expected torch.float64, got {t.dtype}")
+    if tuple(t.shape[1:]) != (R, K):
+        raise ValueError(f"{name}: row width {tuple(t.shape[1:])} != (R, K) = {(R, K)}")
+    if not t.is_cuda:
+        raise ValueError(f"{name}: must be a GPU tensor")
+    if dev is not None and t.device != dev:
+        raise ValueError(f"{name}: on {t.device}, expected {dev}")
+    if not t.is_contiguous():
+        raise ValueError(f"{name}: must be contiguous")
+
+
+def _index(name, t, dtype, shape, dev):
+    if not isinstance(t, torch.Tensor) or t.dtype != dtype:
+        raise ValueError(f"{name}: expected an {str(dtype).replace('torch.', '')} tensor")
+    if t.device != dev:
+        raise ValueError(f"{name}: on {t.device}, expected {dev}")
+    if tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{name}: shape {tuple(t.shape)} != {tuple(shape)}")
+    if not t.is_contiguous():
+        raise ValueError(f"{name}: must be contiguous")
+    return t.data_ptr()
+
+
+def group_rows_sum(table, order, seg_start, seg_end, max_blocks: int = 0, block=None):
+    """Sums of table rows over segments of a row order (csrc/hip/explain.hip; ``ops.reference.group_rows_sum`` is
+    the twin): float64 [G, W], row g the sum of ``table[order[seg_start[g] : seg_end[g]]]``, column by column.
+
+    ``table`` [V, W] float64 (W = K, or R K for an ensemble's interleaved rows), ``order`` int32 [V'] of table rows,
+    ``seg_start`` / ``seg_end`` int64 [G] with 0 <= start <= end <= V'.  A segment is cut into blocks of
+    ``config.GROUP_BLOCK`` members; a block is summed from 0.0 in member order, a segment's block sums are added
+    from 0.0 in block order: plain rounded adds, no atomics, the same bits for every grid.  Everything is checked
+    on the host before the launch (host reads: the bounds of ``order`` and of the segments, the block count);
+    ``G == 0`` launches nothing.  ``max_blocks``: cap on the workgroups per launch (tests: a small cap makes the
+    grid-stride loops wrap).  ``block``: another block size (measurement: scripts/explain_bench.py)."""
+    import operator
+    _max_blocks(max_blocks)
+    GB = operator.index(_CFG.GROUP_BLOCK if block is None else block)
+    if GB < 1:
+        raise ValueError(f"group_rows_sum: block must be >= 1, got {GB}")
+    if not isinstance(table, torch.Tensor) or table.dim() != 2:
+        raise ValueError("table: expected a [V, W] tensor")
+    if table.dtype != torch.float64:
+        raise ValueError(f"table: expected torch.float64, got {table.dtype}")
+    if not table.is_cuda:
+        raise ValueError("table: must be a GPU tensor")
+    if not table.is_contiguous():
+        raise ValueError("table: must be contiguous")
+    dev = table.device
+    V, W = table.shape
+    if W < 1 or V >= 1 << 31:
+        raise ValueError(f"table: shape {tuple(table.shape)} (W >= 1, V < 2^31)")
+    if not isinstance(order, torch.Tensor) or order.dim() != 1:
+        raise ValueError("order: expected a 1-D tensor")
+    n_ord = order.numel()
+    p_ord = _index("order", order, torch.int32, (n_ord,), dev)
+    if not isinstance(seg_start, torch.Tensor) or seg_start.dim() != 1:
+        raise ValueError("seg_start: expected a 1-D tensor")
+    G = seg_start.numel()
+    if G >= 1 << 31:
+        raise ValueError(f"group_rows_sum: {G} segments (G < 2^31)")
+    p_s = _index("seg_start", seg_start, torch.int64, (G,), dev)
+    p_e = _index("seg_end", seg_end, torch.int64, (G,), dev)
+    out = torch.empty((G, W), dtype=torch.float64, device=dev)
+    if G == 0:
+        return out
+    # bounds (host checks before a gather kernel touches memory)
+    if n_ord and (int(order.min()) < 0 or int(order.max()) >= V):
+        raise ValueError("order: index out of range")
+    if int(seg_start.min()) < 0 or int((seg_end - seg_start).min()) < 0 or int(seg_end.max()) > n_ord:
+        raise ValueError(f"seg_start / seg_end: segments must satisfy 0 <= start <= end <= {n_ord}")
+    blk_off = torch.zeros(G + 1, dtype=torch.int64, device=dev)
+    blk_off[1:] = torch.cumsum((seg_end - seg_start + (GB - 1)) // GB, 0)
+    B = int(blk_off[-1])
+    if B >= 1 << 31:
+        raise ValueError(f"group_rows_sum: {B} blocks (B < 2^31)")
+    scratch = torch.empty((max(B, 1), W), dtype=torch.float64, device=dev)
+    lib().group_rows_sum(table.data_ptr(), p_ord, p_s, p_e, blk_off.data_ptr(), int(G), int(B), int(W), int(GB),
+                         scratch.data_ptr(), out.data_ptr(), int(max_blocks), _stream())
+    return out
+
+
+def explain_sides(theta, phi, gsum, doc, word, grow, dflt, max_blocks: int = 0):
+    """Per side the conditional probability of every explained field of its word (csrc/hip/explain.hip;
+    ``ops.reference.explain_sides`` is the twin): ``(cond float64 [n, F], why uint8 [n])`` as new device tensors.
+
+    ``theta`` [D, R, K] / ``phi`` [V, R, K] as ``score_ensemble`` takes them, ``gsum`` [Gtot, R, K] the sums of phi
+    rows over groups (``group_rows_sum``); ``doc`` / ``word`` int32 [n] rows or -1, ``grow`` int32 [n, F] the
+    ``gsum`` row of the side's group of field f or -1.  s is the side's ``score_ensemble`` score (a side without a
+    document takes the default vector), m_f the same expression over the group row, ``cond[i, f] = s / m_f``, NaN
+    where ``word[i] < 0`` or ``grow[i, f] < 0``; ``why[i]`` the lowest f with the lowest non-NaN cond, 255 when
+    there is none.  Everything is checked on the host before the launch; ``n == 0`` launches nothing."""
+    _max_blocks(max_blocks)
+    if not isinstance(theta, torch.Tensor) or theta.dim() != 3:
+        raise ValueError("theta: expected a [rows, R, K] tensor")
+    R, K = int(theta.shape[1]), int(theta.shape[2])
+    if not 1 <= R <= ENSEMBLE_MAX:
+        raise ValueError(f"explain_sides: R must be in [1, {ENSEMBLE_MAX}], got {R}")
+    if K < 1:
+        raise ValueError(f"explain_sides: K must be >= 1, got {K}")
+    _table3("theta", theta, R, K)
+    dev = theta.device
+    _table3("phi", phi, R, K, dev)
+    _table3("gsum", gsum, R, K, dev)
+    if not isinstance(doc, torch.Tensor) or doc.dim() != 1:
+        raise ValueError("doc: expected a 1-D tensor")
+    n = doc.numel()
+    if n >= 1 << 31:
+        raise ValueError(f"explain_sides: {n} sides (n < 2^31)")
+    if not isinstance(grow, torch.Tensor) or grow.dim() != 2:
+        raise ValueError("grow: expected an [n, F] tensor")
+    F = int(grow.shape[1])
+    if not 1 <= F <= _CFG.EXPLAIN_MAX_FIELDS:
+        raise ValueError(f"explain_sides: F must be in [1, {_CFG.EXPLAIN_MAX_FIELDS}], got {F}")
+    p_doc = _index("doc", doc, torch.int32, (n,), dev)
+    p_word = _index("word", word, torch.int32, (n,), dev)
+    p_grow = _index("grow", grow, torch.int32, (n, F), dev)
+    # index bounds (host check before a gather kernel touches memory)
+    if n:
+        for name, idx, lim in (("doc", doc, theta.shape[0]), ("word", word, phi.shape[0]),
+                               ("grow", grow, gsum.shape[0])):
+            if int(idx.max()) >= lim or int(idx.min()) < -1:
+                raise ValueError(f"{name}: index out of range")
+    cond = torch.empty((n, F), dtype=torch.float64, device=dev)
+    why = torch.empty(n, dtype=torch.uint8, device=dev)
+    if n == 0:
+        return cond, why
+    L = lib()
+    if L.ensemble_max() != ENSEMBLE_MAX or L.explain_max_fields() != _CFG.EXPLAIN_MAX_FIELDS:
+        raise RuntimeError("explain_sides: config.ENSEMBLE_MAX / EXPLAIN_MAX_FIELDS differ from the compiled limits")
+    # no group row at all (every grow is -1, checked above): the kernel never reads gsum
+    p_gsum = gsum.data_ptr() if gsum.shape[0] else phi.data_ptr()
+    L.explain_sides(theta.data_ptr(), phi.data_ptr(), p_gsum, R, K, F, float(dflt), p_doc, p_word, p_grow,
+                    int(n), cond.data_ptr(), why.data_ptr(), int(max_blocks), _stream())
+    return cond, why
 
 
 def string_entropy(bytes_u8, offsets, max_blocks: int = 0):

@@ -150,6 +150,91 @@ def score_ensemble(theta, phi, R, K, dflt, doc_a, word_a, doc_b=None, word_b=Non
     return ea, eb, key, (key < tol).to(torch.uint8), votes
 
 
+def group_rows_sum(table, order, seg_start, seg_end, block=None):
+    """Torch twin of ``ops.hip.group_rows_sum`` (csrc/hip/explain.hip) on any device, bit for bit: [G, W] float64,
+    row g the sum of the rows ``table[order[seg_start[g] : seg_end[g]]]`` ([V, W] float64), column by column.
+    The segment is cut into blocks of ``block`` members (``config.GROUP_BLOCK``); a block is summed from 0.0 in
+    member order, the block sums are added from 0.0 in block order -- plain rounded adds.  (A step that a block or
+    a segment does not have adds +0.0, which changes no bit of a sum that started at +0.0.)"""
+    from ..config import GROUP_BLOCK
+    GB = int(GROUP_BLOCK if block is None else block)
+    if GB < 1:
+        raise ValueError(f"group_rows_sum: block must be >= 1, got {GB}")
+    if table.dim() != 2 or table.dtype != torch.float64:
+        raise ValueError("group_rows_sum: table [V, W] float64")
+    V, W = table.shape
+    dev = table.device
+    order = order.reshape(-1).to(torch.int64)
+    s, e = seg_start.reshape(-1).to(torch.int64), seg_end.reshape(-1).to(torch.int64)
+    G = s.numel()
+    if e.numel() != G:
+        raise ValueError("group_rows_sum: seg_start and seg_end differ in length")
+    out = torch.zeros((G, W), dtype=torch.float64, device=dev)
+    if G == 0:
+        return out
+    if int((e - s).min()) < 0 or int(s.min()) < 0 or int(e.max()) > order.numel():
+        raise ValueError("group_rows_sum: segments outside the order")
+    if order.numel() and (int(order.min()) < 0 or int(order.max()) >= V):
+        raise ValueError("group_rows_sum: order out of range")
+    nb = (e - s + (GB - 1)) // GB                                   # blocks of every segment
+    B = int(nb.sum())
+    if B == 0:
+        return out
+    seg = torch.repeat_interleave(torch.arange(G, device=dev), nb)          # the segment of every block
+    first = torch.cumsum(nb, 0) - nb                                        # a segment's first block
+    j = torch.arange(B, device=dev) - first[seg]                            # a block's number in its segment
+    b_start = s[seg] + j * GB
+    b_len = torch.minimum(e[seg] - b_start, torch.full_like(b_start, GB))
+    part = torch.zeros((B, W), dtype=torch.float64, device=dev)
+    zero = torch.zeros((), dtype=torch.float64, device=dev)
+    for m in range(int(b_len.max())):
+        have = b_len > m
+        rows = order[torch.where(have, b_start + m, torch.zeros_like(b_start))]
+        part = part + torch.where(have.unsqueeze(1), table[rows], zero)
+    for k in range(int(nb.max())):
+        have = nb > k
+        out = out + torch.where(have.unsqueeze(1), part[torch.where(have, first + k, torch.zeros_like(first))], zero)
+    return out
+
+
+def explain_sides(theta, phi, gsum, doc, word, grow, dflt):
+    """Torch twin of ``ops.hip.explain_sides`` (csrc/hip/explain.hip) on any device, bit for bit:
+    ``(cond float64 [n, F], why uint8 [n])``.  ``theta`` [D, R, K], ``phi`` [V, R, K], ``gsum`` [Gtot, R, K] (sums
+    of phi rows over groups); ``doc`` / ``word`` [n] rows or -1, ``grow`` [n, F] gsum rows or -1.  With s the
+    side's ``score_ensemble`` score and m_f the same expression over the row ``grow[:, f]`` of ``gsum`` in place of
+    the phi row, ``cond[:, f] = s / m_f`` -- NaN where the side has no phi row or no group row; ``why`` is the
+    lowest f with the lowest non-NaN cond, 255 when there is none.  A side without a document takes the default
+    vector for theta."""
+    if theta.dim() != 3 or phi.dim() != 3 or gsum.dim() != 3 or theta.shape[1:] != phi.shape[1:] \
+            or gsum.shape[1:] != phi.shape[1:]:
+        raise ValueError("explain_sides: theta [D, R, K], phi [V, R, K] and gsum [G, R, K]")
+    if grow.dim() != 2 or grow.shape[0] != doc.numel() or word.numel() != doc.numel():
+        raise ValueError("explain_sides: doc [n], word [n] and grow [n, F]")
+    R, K = int(theta.shape[1]), int(theta.shape[2])
+    n, F = grow.shape
+    dev = doc.device
+    nan = torch.full((), float("nan"), dtype=torch.float64, device=dev)
+    cond = torch.empty((n, F), dtype=torch.float64, device=dev)
+    why = torch.full((n,), 255, dtype=torch.uint8, device=dev)
+    if n == 0:
+        return cond, why
+    has_w = word >= 0
+    s = score_ensemble(theta, phi, R, K, dflt, doc, word.clamp_min(0))[0]
+    best = torch.zeros(n, dtype=torch.float64, device=dev)
+    for f in range(F):
+        g = grow[:, f]
+        if gsum.shape[0]:
+            m = score_ensemble(theta, gsum, R, K, dflt, doc, g.clamp_min(0))[0]
+        else:
+            m = torch.ones_like(s)
+        c = torch.where(has_w & (g >= 0), s / m, nan)
+        cond[:, f] = c
+        take = (c == c) & ((why == 255) | (c < best))      # '<': ties go to the lowest field
+        best = torch.where(take, c, best)
+        why = torch.where(take, torch.full_like(why, f), why)
+    return cond, why
+
+
 def select_lowest(key, flag, limit, with_count: bool = False):
     """Torch twin of ``ops.hip.select_lowest`` (csrc/hip/select_lowest.hip) on any device: the row indices
     (int64, ascending) of the ``limit`` flagged rows that a stable ascending sort of their keys puts first, all

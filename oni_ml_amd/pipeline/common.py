@@ -31,6 +31,8 @@ class ModelTables:
     key_space: Optional[object] = None
     # --ensemble: (θ, φ) of the members 1 .. R-1, rows as in theta / phi (one corpus, one set of names)
     members: Optional[list] = None
+    # --explain: (int64 key of every φ row, the key's fields as ``WordSpace.fields()`` returns them)
+    word_fields: Optional[tuple] = None
 
     def doc_index(self) -> dict:
         return {n: i for i, n in enumerate(self.doc_names)}      # later duplicates win (collectAsMap)
@@ -430,6 +432,94 @@ def write_host_report(cfg, tables: ModelTables, doc_a, score_a, doc_b, score_b, 
     return dict(hosts=int(hosts.size), host_sides_skipped=int(skipped))
 
 
+@dataclass
+class ExplainInput:
+    """What a scorer hands ``write_results`` for --explain, per side of an event (flow: source, destination):
+    ``words`` the φ row of every event's side (-1: none), ``ips`` the (names, id of every event) of the side's
+    document, ``cols`` the positions (word, score) of the side's columns in the scorer's ``row_cols`` list."""
+    model: object
+    words: tuple
+    ips: tuple
+    cols: tuple
+
+
+def save_word_fields(lpath: str, word_keys, fields):
+    """<LPATH>/word_fields.npz (lda_pre under --explain): the int64 word keys in φ-row order and the key's fields,
+    so that a resumed scoring stage can explain too."""
+    from ..config import WORD_FIELDS
+    np.savez(os.path.join(lpath, WORD_FIELDS), keys=np.asarray(word_keys, np.int64),
+             radix=np.asarray([r for _, r, _ in fields], np.int64), names=np.asarray([n for n, _, _ in fields]),
+             explained=np.asarray([bool(e) for _, _, e in fields]))
+
+
+def load_word_fields(lpath: str):
+    """(keys int64 [V], fields) of ``save_word_fields``."""
+    from ..config import WORD_FIELDS
+    with np.load(os.path.join(lpath, WORD_FIELDS), allow_pickle=False) as z:
+        fields = [(str(n), int(r), bool(e)) for n, r, e in zip(z["names"], z["radix"], z["explained"])]
+        return z["keys"].astype(np.int64), fields
+
+
+def write_explain(cfg, tables, order, key, sides, ex: ExplainInput, cols, sep: str = ",", log=print) -> dict:
+    """--explain: ``<type>_explain.csv`` next to the results file, line i describing its line i (``order``: the
+    written events; ``cols``: their ``row_cols``): the key score, then per side the document, the word, the side's
+    score, ``why`` -- the explained field of the word with the lowest conditional probability c_f, empty when
+    there is none -- and c_f of every explained field (empty for NaN).  c_f = s / m_f, m_f the side's score with
+    the φ row replaced by the sum of the φ rows that agree with the word on every field but f
+    (``scorer.field_groups``, ``scorer.explain_sides``).  Returns the summary entries."""
+    from ..ops import native
+    from ..ops import sortgroup as SG
+    from ..score import scorer as S
+    if getattr(tables, "word_fields", None) is None:
+        raise ValueError("--explain: the vocabulary's word keys are not known to the scoring stage")
+    word_keys, fields = tables.word_fields
+    names = [n for n, _, e in fields if e]
+    F = len(names)
+    dev = key.device
+    n = int(order.size)
+    o_t = torch.from_numpy(order).to(dev)
+    n_sides = len(ex.words)
+    doc = torch.cat([SG.gather(sides[2 * j], o_t).to(torch.int64) for j in range(n_sides)]) if n else \
+        torch.zeros(0, dtype=torch.int64, device=dev)
+    word = torch.cat([SG.gather(w, o_t).to(torch.int64) for w in ex.words]) if n else doc
+    cond = np.full((n_sides * n, F), np.nan)
+    why = np.full(n_sides * n, 255, np.uint8)
+    largest = [0] * F      # per explained field the members of the largest group a written side refers to
+    if n:
+        rows, inv = SG.unique(word, return_inverse=True)
+        none = int(rows[0] < 0) if rows.numel() else 0      # the -1 of the sides without a φ row sorts first
+        rows = rows[none:]
+        gsum, grow_u, sizes = S.field_groups(ex.model, torch.from_numpy(np.asarray(word_keys, np.int64)), fields,
+                                             rows)
+        if rows.numel():
+            largest = sizes.max(0).values.cpu().tolist()
+        if rows.numel():
+            grow = torch.where((word >= 0).unsqueeze(1), SG.gather(grow_u, (inv - none).clamp_min(0)),
+                               torch.full((1, 1), -1, dtype=torch.int64, device=dev))
+        else:
+            grow = torch.full((word.numel(), F), -1, dtype=torch.int64, device=dev)
+        c_t, w_t = S.explain_sides(ex.model, gsum, doc, word, grow)
+        cond, why = c_t.cpu().numpy(), w_t.cpu().numpy()
+    out_cols = [("java", SG.gather(key, o_t).cpu().numpy())]
+    for j in range(n_sides):
+        ip_names, ip_ids = ex.ips[j]
+        c, w = cond[j * n:(j + 1) * n], why[j * n:(j + 1) * n]
+        ok = ~np.isnan(c)
+        text = native.lib().java_double_array(np.ascontiguousarray(c[ok], np.float64))
+        idx = np.full(c.shape, -1, np.int32)
+        idx[ok] = np.arange(len(text), dtype=np.int32)
+        out_cols += [("dict", ip_names, SG.gather(ip_ids, o_t).cpu().numpy().astype(np.int32)),
+                     cols[ex.cols[j][0]], cols[ex.cols[j][1]],
+                     ("dict", names, np.where(w == 255, -1, w.astype(np.int32)).astype(np.int32))]
+        out_cols += [("dict", text, np.ascontiguousarray(idx[:, f])) for f in range(F)]
+    out = os.path.join(cfg.lpath, f"{cfg.dsource}_explain.csv")
+    native.lib().write_rows(out, None, out_cols, sep=sep, threads=cfg.threads, n=n)
+    hist = np.bincount(np.where(why == 255, F, why), minlength=F + 1)
+    log(f"{cfg.dsource}_post: {n_sides * n} sides explained in {out}")
+    return dict(explain_fields=names, explain_why_hist=dict(zip(names + ["none"], hist.astype(np.int64).tolist())),
+                explain_max_group=dict(zip(names, (int(x) for x in largest))))
+
+
 def one_sided_index(tables, ip_names, ip, unames, inv, device, ip_map=None):
     """The one-sided scorers' (dns, proxy) index set-up: (θ, φ, θ row of every event, φ row of every event).
     ``ip`` / ``inv``: every event's id into ``ip_names`` / ``unames``; ``ip_map``: the doc row of every ip id
@@ -460,12 +550,13 @@ def rank_results(cfg, key, flag):
 
 
 def write_results(cfg, tables, what: str, ranked, key, row_cols, events: int, sides, votes, log=print, ctx=None,
-                  sep: str = ",", extra=None) -> dict:
+                  sep: str = ",", extra=None, explain: Optional[ExplainInput] = None) -> dict:
     """``<type>_results.csv`` from ``ranked`` (what ``rank_results`` returned) and the scorer's ``row_cols``, the
     log line, and the scoring stage's result.  One process: the rows, then the host report (``sides``: the
     ``doc_a, score_a, doc_b, score_b`` of ``write_host_report``) and the votes histogram.  Several ranks
     (``ctx``): the ranks' rows merged into one ascending file (``shardio.merge_sorted_rows``, the sortByKey
-    shuffle), the counts summed.  ``extra``: further result entries."""
+    shuffle), the counts summed.  ``extra``: further result entries.  ``explain``: the sides' φ rows and columns
+    for ``write_explain`` (one process, under --explain)."""
     from ..ops import native
     order, below, limit = ranked
     n = int(order.size)
@@ -484,8 +575,9 @@ def write_results(cfg, tables, what: str, ranked, key, row_cols, events: int, si
     native.lib().write_rows(out, None, cols, sep=sep, threads=cfg.threads, n=n)
     log(f"{cfg.dsource}_post: {flagged_text(n, below, limit, what, cfg.tol)} written to {out}")
     hosts = write_host_report(cfg, tables, *sides, row_cols, sep=sep, log=log) if cfg.host_report else {}
+    why = write_explain(cfg, tables, order, key, sides, explain, cols, sep=sep, log=log) if cfg.explain else {}
     return dict(flagged=n, below_tol=below, events=events, **(extra or {}), **hosts,
-                **votes_hist(votes, order, cfg.ensemble))
+                **votes_hist(votes, order, cfg.ensemble), **why)
 
 
 def save_json(path: str, obj):

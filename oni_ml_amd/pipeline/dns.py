@@ -46,7 +46,8 @@ def _pre(cfg, inputs, device, res, log):
     C.save_json(os.path.join(cfg.lpath, "dns_cuts.json"), dict(cuts={k: v.tolist() for k, v in feat.cuts.items()}))
     res["pairs"] = dwc.n
     log("cuts: " + " ".join(f"{k}={v.tolist()}" for k, v in feat.cuts.items()))
-    return Pre(dwc, feat.ip_names, wsp.decode, keep=feat.host)      # dns_post takes its raw rows' slice
+    # keep: dns_post takes its raw rows' slice
+    return Pre(dwc, feat.ip_names, wsp.decode, keep=feat.host, fields=wsp.fields())
 
 
 def _post(cfg, inputs, tables, device, log, pre):
@@ -108,7 +109,8 @@ def score_dns(cfg, tab: FD.DnsTable, top, tables: C.ModelTables, device, log=pri
             ("java", sc[o_t].cpu().numpy()),
         ]
     return C.write_results(cfg, tables, "queries", ranked, key, row_cols, int(feat.word_key.numel()),
-                           (didx, sc, None, None), votes, log, ctx=ctx)
+                           (didx, sc, None, None), votes, log, ctx=ctx,
+                           explain=C.ExplainInput(model, (widx,), ((feat.ip_names, feat.ip),), ((-2, -1),)))
 
 
 def synthetic_dns_corpus(events: int = 2_000_000, seed: int = 0, device=None, strict: bool = True, threads: int = 8,

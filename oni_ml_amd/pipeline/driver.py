@@ -22,6 +22,7 @@ class Pre:
     ip_names: List[str]                   # name of every ip dictionary id (documents are a subset)
     decode: Callable                      # word keys -> word names
     keep: object = None                   # what the scoring stage reuses when it runs in the same process
+    fields: Optional[list] = None         # the word key's fields (``WordSpace.fields()``), for --explain
     built: Optional[BuiltCorpus] = None   # set by lda_pre
     exported: bool = False                # lda_post ran in this process: the tables' rows are ``built``'s
 
@@ -57,11 +58,13 @@ def lda_stage(R, cfg, corpus, device, log, summary, dist=None, local_shard=False
     return lres
 
 
-def _write_lda_pre_files(lpath, built, doc_names, word_names, dwc_h, ip_names):
+def _write_lda_pre_files(lpath, built, doc_names, word_names, dwc_h, ip_names, fields=None):
     if dwc_h is not None:
         from ..corpus.builder import write_doc_wc
         write_doc_wc(os.path.join(lpath, "doc_wc.dat"), dwc_h, ip_names, C.vocab_lookup(built.word_keys, word_names))
     C.write_corpus_files(lpath, built, doc_names, word_names)
+    if fields is not None:      # --explain: a resumed scoring stage reads the keys from here
+        C.save_word_fields(lpath, built.word_keys, fields)
 
 
 def run_stages(cfg, spec: PipelineSpec, device=None, log=print) -> dict:
@@ -71,8 +74,16 @@ def run_stages(cfg, spec: PipelineSpec, device=None, log=print) -> dict:
     pre_stage, post_stage = spec.name + "_pre", spec.name + "_post"
     summary = {}
     inputs = pre = corpus = doc_names = word_names = None
-    ens = C.Ensemble(cfg, R, post_stage, device, log)      # --ensemble; inert with one model
     need_pre = not (R.done("lda_pre") and R.done(pre_stage))
+    if cfg.explain and not need_pre:
+        # a resumed scoring stage explains from the keys lda_pre wrote: refused here, before any stage runs and
+        # before a marker is touched
+        from ..config import WORD_FIELDS
+        path = os.path.join(cfg.lpath, WORD_FIELDS)
+        if not os.path.exists(path):
+            raise ValueError(f"--resume --explain: {path} is missing (lda_pre ran without --explain); "
+                             "run again from scratch with --explain")
+    ens = C.Ensemble(cfg, R, post_stage, device, log)      # --ensemble; inert with one model
     if need_pre or not R.done(post_stage):
         with R.stage("load") as res:
             inputs = spec.load(cfg, res, summary, log)
@@ -88,7 +99,8 @@ def run_stages(cfg, spec: PipelineSpec, device=None, log=print) -> dict:
             dwc_h = pre.dwc.to_host() if cfg.write_doc_wc else None
             # the text files are the stage contract, not an input of the in-memory lda stage: written on a
             # thread while the GPU runs EM; the lda_pre marker waits for them (finish_deferred)
-            files = (cfg.lpath, built, doc_names, word_names, dwc_h, pre.ip_names)
+            files = (cfg.lpath, built, doc_names, word_names, dwc_h, pre.ip_names,
+                     pre.fields if cfg.explain else None)
             res["_defer"] = C.background(lambda: _write_lda_pre_files(*files), "oni-lda-pre-writer")
             size = dict(docs=corpus.num_docs, terms=corpus.num_terms, nnz=corpus.nnz)
             res.update(size)
@@ -137,12 +149,19 @@ def run_stages(cfg, spec: PipelineSpec, device=None, log=print) -> dict:
 
         if not R.done(post_stage):
             with R.stage(post_stage) as res:
+                if cfg.explain:      # the keys of the φ rows: this process's vocabulary, or what lda_pre wrote
+                    tables.word_fields = ((pre.built.word_keys, pre.fields) if pre is not None
+                                          else C.load_word_fields(cfg.lpath))
                 res.update(spec.post(cfg, inputs, tables, device, log, pre))
                 summary["scored"] = res.get("flagged")
                 summary["below_tol"] = res.get("below_tol")
                 if cfg.host_report:
                     summary["hosts"], summary["host_sides_skipped"] = res.get("hosts"), res.get("host_sides_skipped")
                 ens.scored(res, summary)
+                if cfg.explain:
+                    why = {k: res[k] for k in ("explain_fields", "explain_why_hist", "explain_max_group")}
+                    summary.update(why)
+                    R.emit(dict(stage=post_stage + "_detail", **why))
         else:
             R.skip(post_stage)
     except BaseException:

@@ -58,7 +58,7 @@ def _pre(cfg, ft, device, res, log):
     res["pairs"] = dwc.n
     log(f"cuts: time={feat.cuts['time'].tolist()} ibyt={feat.cuts['ibyt'].tolist()} "
         f"ipkt={feat.cuts['ipkt'].tolist()}")
-    return Pre(dwc, ft.ip_names, ws.decode, keep=ws)
+    return Pre(dwc, ft.ip_names, ws.decode, keep=ws, fields=ws.fields())
 
 
 def _post(cfg, ft, tables, device, log, pre):
@@ -165,7 +165,9 @@ def score_flow(cfg, ft: FF.FlowTable, tables: C.ModelTables, device, log=print, 
             ("java", sel(sb)),
         ]
     return C.write_results(cfg, tables, "events", ranked, key, row_cols, int(feat.time.numel()),
-                           (d_src, sa, d_dst, sb), votes, log, ctx=ctx, extra=qs)
+                           (d_src, sa, d_dst, sb), votes, log, ctx=ctx, extra=qs,
+                           explain=C.ExplainInput(model, (w_src, w_dst), ((ipn, feat.sip), (ipn, feat.dip)),
+                                                  ((-4, -2), (-3, -1))))
 
 
 def synthetic_flow_corpus(events: int = 1_000_000, seed: int = 0, workdir: Optional[str] = None, device=None,

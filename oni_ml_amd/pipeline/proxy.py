@@ -42,7 +42,8 @@ def _pre(cfg, inputs, device, res, log):
     C.save_json(os.path.join(cfg.lpath, "proxy_cuts.json"), dict(cuts={k: v.tolist() for k, v in feat.cuts.items()}))
     res["pairs"] = dwc.n
     log("cuts: " + " ".join(f"{k}={v.tolist()}" for k, v in feat.cuts.items()))
-    return Pre(dwc, feat.ip_names, wsp.decode, keep=feat.host)      # the cut-independent features: reused
+    # keep: the cut-independent features, reused
+    return Pre(dwc, feat.ip_names, wsp.decode, keep=feat.host, fields=wsp.fields())
 
 
 def _post(cfg, inputs, tables, device, log, pre):
@@ -85,4 +86,5 @@ def score_proxy(cfg, tab: FP.ProxyTable, top, tables: C.ModelTables, device, log
             ("java", SG.gather(sc, o_t).cpu().numpy()),
         ]
     return C.write_results(cfg, tables, "requests", ranked, key, row_cols, int(feat.word_key.numel()),
-                           (didx, sc, None, None), votes, log, sep="\t")
+                           (didx, sc, None, None), votes, log, sep="\t",
+                           explain=C.ExplainInput(model, (widx,), ((feat.ip_names, feat.ip),), ((-2, -1),)))

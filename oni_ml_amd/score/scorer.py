@@ -163,6 +163,87 @@ def host_summary(doc_a, score_a, doc_b, score_b, num_docs: int, tol: float):
     return ref(i32(doc_a), f64(score_a), i32(doc_b), f64(score_b), int(num_docs), float(tol))
 
 
+def group_rows_sum(table: torch.Tensor, order: torch.Tensor, seg_start: torch.Tensor, seg_end: torch.Tensor):
+    """[G, W] sums of the rows ``table[order[seg_start[g] : seg_end[g]]]`` in the fixed block order of
+    ``config.GROUP_BLOCK`` (``ops.hip.group_rows_sum`` on the GPU, ``ops.reference.group_rows_sum`` elsewhere:
+    the same bits)."""
+    if table.device.type == "cuda":
+        from ..ops import hip as H
+        return H.group_rows_sum(table.contiguous(), order.to(torch.int32).contiguous(),
+                                seg_start.to(torch.int64).contiguous(), seg_end.to(torch.int64).contiguous())
+    from ..ops.reference import group_rows_sum as ref
+    return ref(table, order, seg_start, seg_end)
+
+
+def model_tables3(model):
+    """(theta [D, R, K], phi [V, R, K]) of either model kind (one model: R = 1, a view)."""
+    if isinstance(model, EnsembleModel):
+        return model.theta, model.phi
+    return model.theta.unsqueeze(1), model.phi.unsqueeze(1)
+
+
+def field_groups(model, word_keys: torch.Tensor, fields, rows: torch.Tensor):
+    """--explain: for the φ rows ``rows`` (int64, distinct, >= 0) and every explained field of ``fields``
+    (``WordSpace.fields()``: (name, radix, explained), most significant digit first), the sum of φ over the row's
+    group -- the φ rows whose key (``word_keys`` int64 [V], φ-row order) agrees with the row's on every digit but
+    that field's.  Returns ``(gsum [Gtot, R, K], grow int64 [len(rows), F], sizes int64 [len(rows), F])``:
+    ``grow[i, f]`` the ``gsum`` row of ``rows[i]``'s group of the f-th explained field, ``sizes`` its members.
+
+    On the device, from ``ops/sortgroup.py`` primitives only: per field one stable int64 sort of the V masked
+    keys (ties keep row order), the runs' starts, and the segments the given rows reference -- at most
+    len(rows) x F group sums are made, never V x K per field."""
+    from ..ops import sortgroup as SG
+    theta, phi = model_tables3(model)
+    V, R, K = phi.shape
+    dev = phi.device
+    if word_keys.numel() != V:
+        raise ValueError(f"field_groups: {word_keys.numel()} word keys for {V} phi rows")
+    radix = [int(r) for _, r, _ in fields]
+    stride = [1] * len(fields)
+    for i in range(len(fields) - 2, -1, -1):
+        stride[i] = stride[i + 1] * radix[i + 1]
+    keys = word_keys.to(dev).to(torch.int64)
+    flat = phi.reshape(V, R * K)
+    orders, starts, ends, grows, sizes, base = [], [], [], [], [], 0
+    for i, (_, r, explained) in enumerate(fields):
+        if not explained:
+            continue
+        digit = keys // stride[i]
+        if i > 0:      # the most significant digit is whatever remains of the key
+            digit = digit % r
+        sk, perm = SG.sort_stable(keys - digit * stride[i])      # by (masked key, row)
+        grp, G = SG.run_ids(sk)
+        st = SG.run_starts(grp, G)
+        of_row = torch.empty_like(grp)
+        of_row[perm] = grp                                       # the group of every φ row
+        ug, inv = SG.unique(SG.gather(of_row, rows), return_inverse=True)
+        s, e = SG.gather(st, ug), SG.gather(st, ug + 1)
+        # the fields' sorted orders lie back to back: field number len(orders) starts at that many times V
+        starts.append(s + len(orders) * V)
+        ends.append(e + len(orders) * V)
+        orders.append(perm.to(torch.int32))
+        grows.append(inv + base)
+        sizes.append(SG.gather(e - s, inv))
+        base += int(ug.numel())
+    if not orders:
+        raise ValueError("field_groups: no explained field")
+    # one launch pair (and one set of host-side bound checks) for every field's groups
+    gsum = group_rows_sum(flat, torch.cat(orders), torch.cat(starts), torch.cat(ends)).reshape(-1, R, K)
+    return gsum, torch.stack(grows, 1), torch.stack(sizes, 1)
+
+
+def explain_sides(model, gsum: torch.Tensor, doc: torch.Tensor, word: torch.Tensor, grow: torch.Tensor):
+    """``(cond [n, F], why uint8 [n])`` of the sides (``ops.hip.explain_sides`` on the GPU, its torch twin
+    elsewhere); ``model``: a TopicModel or an EnsembleModel."""
+    theta, phi = model_tables3(model)
+    i32 = lambda t: t.to(torch.int32).contiguous()      # noqa: E731
+    if theta.device.type == "cuda":
+        from ..ops.hip import explain_sides as fn
+    else:
+        from ..ops.reference import explain_sides as fn
+    return fn(theta.contiguous(), phi.contiguous(), gsum.contiguous(), i32(doc), i32(word), i32(grow), model.default)
+
+
 def rank_hosts(min_score: torch.Tensor, flagged: torch.Tensor, limit: Optional[int] = None) -> np.ndarray:
     """Document rows with at least one flagged side, ascending by their lowest score, ties to the lowest row
     (int64 host array); ``limit``: only the first ``limit`` of them (the MAXRESULTS radix select and its tie
