@@ -213,6 +213,19 @@ PYBIND11_MODULE(_onihip, m) {
     oni::launch_explain_sides(a, max_blocks, S(stream));
   });
 
+  m.def("holdout_draw", [](u base, u counts, u chunk_off, int64_t nnz, int64_t chunks, unsigned long long key,
+                           unsigned long long thr, int lane_tokens, u t, int max_blocks, u stream) {
+    oni::HoldoutDrawArgs a{P<const int64_t>(base), P<const int64_t>(counts), P<const int64_t>(chunk_off), nnz, chunks,
+                           key, thr, lane_tokens, P<int64_t>(t)};
+    oni::launch_holdout_draw(a, max_blocks, S(stream));
+  });
+  m.def("holdout_entries", [](u theta, u phi, int K, u doc, u word, u t, u seen, int64_t n, u ll, int max_blocks,
+                              u stream) {
+    oni::HoldoutEntriesArgs a{P<const double>(theta), P<const double>(phi), K, P<const int>(doc), P<const int>(word),
+                              P<const int64_t>(t), P<const uint8_t>(seen), n, P<double>(ll)};
+    oni::launch_holdout_entries(a, max_blocks, S(stream));
+  });
+
   m.def("string_entropy", [](u bytes, u offsets, int64_t n, u table, int64_t table_len, u out, int max_blocks,
                              u stream) {
     if (n < 0 || table_len < 2 || max_blocks < 0) throw std::runtime_error("string_entropy: bad sizes");

@@ -328,6 +328,42 @@ struct ExplainArgs {
 // max_blocks: cap on the workgroups (0: 8192)
 void launch_explain_sides(const ExplainArgs& a, int max_blocks, hipStream_t s);
 
+// --holdout (holdout.hip).  holdout_draw: t[e] = the tokens j of CSR entry e, 0 <= j < counts[e], with
+// splitmix64(key ^ (base[e] + j)) >> 11 < thr -- integers only, so t depends on nothing but (key, thr, corpus).
+// An entry of at most lane_tokens tokens is drawn by one lane; a longer one is cut into chunks of
+// 64 * lane_tokens tokens, a wave per chunk (lanes stride over the tokens, ballot popcount per step), and the
+// chunk counts of an entry of several chunks are added with an integer atomic.
+struct HoldoutDrawArgs {
+  const int64_t* base;        // [nnz] exclusive prefix sum of counts
+  const int64_t* counts;      // [nnz] >= 0 (checked on the host)
+  const int64_t* chunk_off;   // [nnz + 1] exclusive prefix sum of the chunks of the entries over lane_tokens
+  int64_t nnz;                // entries, 0 <= nnz < 2^31
+  int64_t chunks;             // chunk_off[nnz], < 2^31
+  unsigned long long key;     // splitmix64(seed ^ salt), from the host
+  unsigned long long thr;     // 0 < thr <= 2^52
+  int lane_tokens;            // >= 1
+  int64_t* t;                 // [nnz]
+};
+// max_blocks: cap on the workgroups per launch (0: 8192)
+void launch_holdout_draw(const HoldoutDrawArgs& a, int max_blocks, hipStream_t s);
+
+// holdout_entries: ll[e] = (double)t[e] * log_rn(theta[doc[e]] . phi[word[e]]) where t[e] > 0 and
+// seen[word[e]] != 0, else 0.0.  The dot is score_events' (score_dot.h); log_rn is a natural log of correctly
+// rounded fp64 operations in a fixed order (ops/reference.py log_rn is its torch twin).
+struct HoldoutEntriesArgs {
+  const double* theta;   // [D][K]
+  const double* phi;     // [V][K]
+  int K;                 // >= 1
+  const int* doc;        // [n] theta row of the entry, in [0, D) (checked on the host)
+  const int* word;       // [n] phi row of the entry, in [0, V) (checked on the host)
+  const int64_t* t;      // [n] held-out tokens of the entry
+  const uint8_t* seen;   // [V] non-zero: the word has a training entry
+  int64_t n;             // 0 <= n < 2^31
+  double* ll;            // [n]
+};
+// max_blocks: cap on the workgroups (0: 8192)
+void launch_holdout_entries(const HoldoutEntriesArgs& a, int max_blocks, hipStream_t s);
+
 // Byte entropy of every string of a batch (string_entropy.hip): out[i] = (t[n] - sum_b t[c_b]) / n over the
 // bytes [offsets[i], offsets[i + 1]) of `bytes`, t = table (c log2 c, host-built), 0 for n <= 1.
 struct StringEntropyArgs {

@@ -35,6 +35,7 @@
 #include <stdexcept>
 #include <string>
 
+#include "../common/splitmix64.h"
 #include "alpha_newton.h"
 #include "common.h"
 #include "em_control.h"
@@ -172,16 +173,10 @@ __global__ __launch_bounds__(256) void gs_suff64(const int* __restrict__ word_pt
 // lda-c "random" start (random_initialize_ss): class_word[k][w] = 1/V + u, u ~ U[0, 1) from a
 // counter-based generator, so the host (csrc/native, CPU backends) and the device produce the same
 // bits without a host-side stream: u = splitmix64(splitmix64(seed) ^ (k V + w)) >> 11, x 2^-53.
-__device__ __forceinline__ unsigned long long smix64(unsigned long long x) {
-  x += 0x9E3779B97F4A7C15ull;
-  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-  return x ^ (x >> 31);
-}
-
+// (splitmix64: csrc/common/splitmix64.h, shared with the host twin and the holdout draw)
 __global__ __launch_bounds__(256) void init_random_ss_kernel(double* __restrict__ cw, int V, int K, int KS,
                                                              unsigned long long seed) {
-  const unsigned long long s = smix64(seed);
+  const unsigned long long s = splitmix64(seed);
   const double inv = 1.0 / (double)V;
   const long long total = (long long)V * KS;
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total;
@@ -189,7 +184,7 @@ __global__ __launch_bounds__(256) void init_random_ss_kernel(double* __restrict_
     const int w = (int)(i / KS), k = (int)(i % KS);
     double v = 0.0;
     if (k < K) {
-      const unsigned long long h = smix64(s ^ ((unsigned long long)k * (unsigned long long)V + (unsigned long long)w));
+      const unsigned long long h = splitmix64(s ^ ((unsigned long long)k * (unsigned long long)V + (unsigned long long)w));
       v = inv + (double)(h >> 11) * 0x1.0p-53;
     }
     cw[i] = v;

@@ -15,24 +15,9 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "score_dot.h"   // score_one, shared with holdout.hip
 
 namespace oni {
-
-__device__ __forceinline__ double score_one(const double* __restrict__ theta, const double* __restrict__ phi,
-                                            int K, double dflt, int d, int w) {
-  // HIP compiles with -ffp-contract=fast; the JVM rounds the product and the sum separately.
-#pragma clang fp contract(off)
-  const double* tr = d >= 0 ? theta + (size_t)d * K : nullptr;
-  const double* pr = w >= 0 ? phi + (size_t)w * K : nullptr;
-  double s = 0.0;
-  for (int k = 0; k < K; ++k) {
-    const double tk = tr ? tr[k] : dflt;
-    const double pk = pr ? pr[k] : dflt;
-    const double prod = tk * pk;  // contract(off): rounded product, then rounded sum
-    s = s + prod;
-  }
-  return s;
-}
 
 __global__ __launch_bounds__(256) void score_events_kernel(ScoreArgs a) {
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.n;

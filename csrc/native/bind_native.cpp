@@ -15,6 +15,7 @@
 #include <limits>
 #include <thread>
 
+#include "../common/splitmix64.h"
 #include "corpus_io.h"
 #include "dns.h"
 #include "engine_plan.h"
@@ -849,12 +850,7 @@ PYBIND11_MODULE(_oninative, m) {
         if (threads <= 0) threads = default_threads();
         {
           py::gil_scoped_release rel;
-          auto mix = [](unsigned long long x) {
-            x += 0x9E3779B97F4A7C15ull;
-            x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-            x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-            return x ^ (x >> 31);
-          };
+          auto mix = [](unsigned long long x) { return oni::splitmix64(x); };
           const unsigned long long s = mix(seed);
           const double inv = 1.0 / (double)V;
           const long long total = (long long)K * V;

@@ -137,7 +137,7 @@ def native_flags():
 def build_hip(verbose=False, jobs=8) -> Path:
     """Compile csrc/hip/*.hip (device kernels, gfx950) + bind_hip.cpp into _onihip."""
     out = LIB / ("_onihip" + _ext_suffix())
-    hdrs = sorted((CSRC / "hip").glob("*.h"))
+    hdrs = sorted((CSRC / "hip").glob("*.h")) + sorted((CSRC / "common").glob("*.h"))
     srcs = sorted((CSRC / "hip").glob("*.hip"))
     bind = CSRC / "hip" / "bind_hip.cpp"
     flags = hip_flags()
@@ -159,7 +159,8 @@ def build_native(verbose=False, jobs=8) -> Path:
     """Compile csrc/native/*.cpp (host runtime) into _oninative + the `lda` CLI binary."""
     cxx = os.environ.get("CXX", "g++")
     out = LIB / ("_oninative" + _ext_suffix())
-    hdrs = sorted((CSRC / "native").glob("*.h"))
+    # csrc/common: plain C++ shared with the HIP side (splitmix64.h)
+    hdrs = sorted((CSRC / "native").glob("*.h")) + sorted((CSRC / "common").glob("*.h"))
     # every .cpp of csrc/native (engine_plan.cpp, the fp64 engine's host planner, included) but the programs
     # with a main of their own
     srcs = [s for s in sorted((CSRC / "native").glob("*.cpp"))

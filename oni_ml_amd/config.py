@@ -26,7 +26,8 @@ from typing import Dict, List, Optional
 from .models.lda.settings import LDASettings
 
 ENV_KEYS = ("FLOW_PATH", "DNS_PATH", "PROXY_PATH", "HPATH", "LPATH", "LUSER", "TOL", "DUPFACTOR", "KRB_AUTH", "NODES",
-            "UINODE", "RPATH", "LDAPATH", "SPK_EXEC", "SPK_EXEC_MEM", "TOP1M", "CUT", "MAXRESULTS", "ENSEMBLE", "EXPLAIN")
+            "UINODE", "RPATH", "LDAPATH", "SPK_EXEC", "SPK_EXEC_MEM", "TOP1M", "CUT", "MAXRESULTS", "ENSEMBLE", "EXPLAIN",
+            "HOLDOUT", "HOLDOUT_TOPICS")
 
 # proxy has no multi-rank, sharded or HDFS-staged form
 PROXY_ONE_PROCESS = "proxy runs on one process: launch it without torchrun, with --gpus 1 and without --hdfs"
@@ -46,6 +47,17 @@ EXPLAIN_MAX_FIELDS = 8     # explained fields of a word space (csrc/hip/kernels.
 # block in member order, then the block sums in block order; the value is part of the result's bits
 GROUP_BLOCK = 256
 WORD_FIELDS = "word_fields.npz"      # <LPATH>/word_fields.npz: the vocabulary's keys and fields, under --explain
+
+# --holdout: the split and the K fits are one process's: no multi-rank, sharded or HDFS-staged form
+HOLDOUT_ONE_PROCESS = "--holdout runs on one process: launch it without torchrun, with --gpus 1 and without --hdfs"
+HOLDOUT_DIR = "holdout"              # <LPATH>/holdout/: holdout.csv, holdout.json, k<K>/ (the K's training fit)
+HOLDOUT_MAX_F = 0.5
+HOLDOUT_MIN_TOKENS = 10              # a document of fewer tokens is not split
+# tokens of a corpus entry one lane draws (ops.hip.holdout_draw); a longer entry is shared by waves, 64 lanes x
+# this many tokens each.  The split does not depend on it.
+HOLDOUT_LANE_TOKENS = 64
+HOLDOUT_SALT = 0x686F6C646F757421    # "holdout!": key = splitmix64(seed ^ HOLDOUT_SALT)
+HOLDOUT_HIP_MAX_TOPICS = 128         # largest topic count of the HIP engine (ops.hip.padded_topics)
 
 _VAR = re.compile(r"\$\{([A-Za-z_][A-Za-z0-9_]*)\}|\$([A-Za-z_][A-Za-z0-9_]*)")
 
@@ -103,6 +115,10 @@ class RunConfig:
                                           # side under TOL, N >= 1: the N hosts with the lowest scores
     explain: bool = False                 # --explain / EXPLAIN: also write <type>_explain.csv, per written side the
                                           # field of its word that makes it rare
+    holdout: float = 0.0                  # --holdout / HOLDOUT: hold this fraction of every document's tokens out, fit
+                                          # on the rest and report the held-out perplexity per topic count; 0: off
+    holdout_topics: str = ""              # --holdout-topics / HOLDOUT_TOPICS: "K1,K2,..." to evaluate; "": topics alone
+    holdout_select: bool = False          # --holdout-select: fit the day with the evaluated K of lowest perplexity
     lpath: str = ""                       # local working dir (reference: ${LUSER}/ml/${FDATE})
     hpath: str = ""                       # HDFS dir in the reference; unused unless set (optional copy target)
     flow_path: str = ""
@@ -178,7 +194,42 @@ class RunConfig:
         if self.explain and (self.gpus > 1 or self.hdfs):
             raise ValueError(EXPLAIN_ONE_PROCESS)
         self.check_ensemble(self.ensemble, self.start, self.gpus, self.hdfs)
+        self.check_holdout(self.holdout, self.holdout_list(), self.holdout_select, self.start, self.compat,
+                           self.dsource, self.backend, self.gpus, self.hdfs)
         return self
+
+    def holdout_list(self) -> List[int]:
+        """The topic counts --holdout evaluates, in the order given: ``holdout_topics``, else ``topics`` alone."""
+        return parse_topic_list(self.holdout_topics) or [int(self.topics)]
+
+    @staticmethod
+    def check_holdout(holdout: float, topics: List[int], select: bool, start: str, compat: str, dsource: str,
+                      backend: str = "auto", gpus: int = 1, hdfs: bool = False, world: int = 1):
+        """The --holdout rules, also applied by the command line before anything is written."""
+        holdout = float(holdout)
+        if holdout == 0.0:
+            if select:
+                raise ValueError("--holdout-select needs --holdout F")
+            return
+        if not 0.0 < holdout <= HOLDOUT_MAX_F:      # (a NaN fails both comparisons)
+            raise ValueError(f"--holdout must be in (0, {HOLDOUT_MAX_F}], got {holdout}")
+        if gpus > 1 or world > 1 or hdfs:
+            raise ValueError(HOLDOUT_ONE_PROCESS)
+        if start not in ("random", "seeded"):
+            raise ValueError(f"--holdout needs a random or seeded start: the model {start!r} fixes the topic count")
+        if len(set(topics)) != len(topics):
+            raise ValueError(f"--holdout-topics names a topic count twice: {topics}")
+        hip = backend == "hip"
+        if backend == "auto" and any(k > HOLDOUT_HIP_MAX_TOPICS for k in topics):
+            import torch
+            hip = torch.cuda.is_available()
+        for k in topics:
+            if k < 1 or (hip and k > HOLDOUT_HIP_MAX_TOPICS):
+                raise ValueError(f"--holdout-topics: {k} is outside what the {backend} backend fits "
+                                 f"(1 .. {HOLDOUT_HIP_MAX_TOPICS if hip else 'any'})")
+        if select and compat == "strict" and dsource in ("flow", "dns") and any(k != 20 for k in topics):
+            raise ValueError("--holdout-select under --compat strict: the strict flow and dns scorers are fixed at 20 "
+                             f"topics, the list {topics} could select another; use --compat fixed")
 
     @staticmethod
     def check_ensemble(ensemble: int, start: str, gpus: int = 1, hdfs: bool = False, world: int = 1):
@@ -196,6 +247,17 @@ class RunConfig:
     def to_dict(self) -> dict:
         d = asdict(self)
         return d
+
+
+def parse_topic_list(x) -> List[int]:
+    """"10,20,30" (or a list) -> [10, 20, 30]; "" / None -> []."""
+    if x is None or x == "":
+        return []
+    items = x.split(",") if isinstance(x, str) else list(x)
+    try:
+        return [int(str(i).strip()) for i in items if str(i).strip() != ""]
+    except ValueError:
+        raise ValueError(f"--holdout-topics must be a comma-separated list of topic counts, got {x!r}") from None
 
 
 def resolve(fdate: str, dsource: str, tol: Optional[float] = None, conf_path: Optional[str] = None,
@@ -242,6 +304,11 @@ def _apply(cfg: RunConfig, layer: Dict[str, object]):
         cfg.ensemble = int(layer["ENSEMBLE"])
     if "EXPLAIN" in layer and layer["EXPLAIN"] not in ("", None):
         cfg.explain = str(layer["EXPLAIN"]).strip().lower() not in ("0", "false", "no", "off")
+    if "HOLDOUT" in layer and layer["HOLDOUT"] not in ("", None):
+        cfg.holdout = float(layer["HOLDOUT"])
+    if "HOLDOUT_TOPICS" in layer and layer["HOLDOUT_TOPICS"] not in ("", None):
+        t = layer["HOLDOUT_TOPICS"]
+        cfg.holdout_topics = ",".join(t) if isinstance(t, list) else str(t)      # a bash array or "10,20"
     if "DUPFACTOR" in layer and layer["DUPFACTOR"] not in ("", None):
         cfg.dupfactor = int(layer["DUPFACTOR"])
     if "CUT" in layer and isinstance(layer["CUT"], str) and layer["CUT"].strip():

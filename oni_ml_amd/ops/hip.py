@@ -603,6 +603,95 @@ def explain_sides(theta, phi, gsum, doc, word, grow, dflt, max_blocks: int = 0):
     return cond, why
 
 
+def holdout_draw(doc_ptr, counts, seed, thr, max_blocks: int = 0, rules: bool = True, lane_tokens=None):
+    """Held-out tokens of every CSR entry (csrc/hip/holdout.hip; ``ops.reference.holdout_draw`` is the twin): int64
+    [nnz] as a new device tensor.
+
+    ``doc_ptr`` int64 [D + 1], ``counts`` int64 [nnz] >= 0, on the GPU.  Token j of entry e has the global index
+    ``g = base[e] + j`` (base: the exclusive prefix sum of the counts) and is held out iff
+    ``splitmix64(key ^ g) >> 11 < thr``, ``key = reference.holdout_key(seed)``, ``0 < thr <= 2**52``
+    (``reference.holdout_thr(F)``): integers only, the same split for every grid.  An entry of at most
+    ``config.HOLDOUT_LANE_TOKENS`` tokens is drawn by one lane, a longer one by waves of 64 lanes x that many
+    tokens.  ``rules``: then the two document rules (``reference.holdout_rules``; False: the raw draw).
+    Everything is checked on the host before the launch (host reads: the ends of ``doc_ptr``, the bounds of
+    ``counts``, the token total, the chunk count); an empty corpus launches nothing.  ``max_blocks``: cap on the
+    workgroups per launch (tests: a small cap makes the grid-stride loops wrap).  ``lane_tokens``: another lane
+    share (measurement: scripts/holdout_bench.py)."""
+    import operator
+
+    from . import reference as REF
+    _max_blocks(max_blocks)
+    L = operator.index(_CFG.HOLDOUT_LANE_TOKENS if lane_tokens is None else lane_tokens)
+    if not 1 <= L <= 1 << 20:
+        raise ValueError(f"holdout_draw: lane_tokens must be in [1, 2^20], got {L}")
+    for name, x in (("doc_ptr", doc_ptr), ("counts", counts)):
+        if isinstance(x, torch.Tensor) and not x.is_cuda:
+            raise ValueError(f"{name}: must be a GPU tensor")
+    REF.check_holdout_draw(doc_ptr, counts, seed, thr)      # dtypes, contiguity, one device, values
+    dev = counts.device
+    nnz = counts.numel()
+    t = torch.empty(nnz, dtype=torch.int64, device=dev)
+    if nnz == 0:
+        return t
+    base = torch.cumsum(counts, 0) - counts
+    chunk_off = torch.zeros(nnz + 1, dtype=torch.int64, device=dev)
+    span = 64 * L
+    chunk_off[1:] = torch.cumsum(torch.where(counts > L, (counts + (span - 1)) // span, torch.zeros_like(counts)), 0)
+    chunks = int(chunk_off[-1])
+    if chunks >= 1 << 31:
+        raise ValueError(f"holdout_draw: {chunks} wave chunks (< 2^31); raise lane_tokens")
+    lib().holdout_draw(base.data_ptr(), counts.data_ptr(), chunk_off.data_ptr(), int(nnz), chunks,
+                       REF.holdout_key(seed), operator.index(thr), int(L), t.data_ptr(), int(max_blocks), _stream())
+    return REF.holdout_rules(doc_ptr, counts, t) if rules else t
+
+
+def holdout_entries(theta, phi, doc, word, t, word_seen, max_blocks: int = 0):
+    """Held-out log-likelihood of every CSR entry (csrc/hip/holdout.hip; ``ops.reference.holdout_entries`` is the
+    twin): float64 [n] as a new device tensor, ``t[e] * log_rn(theta[doc[e]] . phi[word[e]])`` for an entry with
+    ``t[e] > 0`` whose word has a training entry (``word_seen[word[e]] != 0``), else 0.0.
+
+    ``theta`` [D, K] / ``phi`` [V, K] float64, ``doc`` / ``word`` int32 [n] rows (no -1 here: every entry has its
+    document and its word), ``t`` int64 [n], ``word_seen`` uint8 [V].  The dot is ``score_events``'; ``log_rn`` a
+    natural log of correctly rounded fp64 operations in a fixed order.  Everything is checked on the host before
+    the launch; ``n == 0`` launches nothing."""
+    _max_blocks(max_blocks)
+    for name, x in (("theta", theta), ("phi", phi)):
+        if not isinstance(x, torch.Tensor) or x.dim() != 2:
+            raise ValueError(f"{name}: expected a [rows, K] tensor")
+        if x.dtype != torch.float64:
+            raise ValueError(f"{name}: expected torch.float64, got {x.dtype}")
+        if not x.is_cuda:
+            raise ValueError(f"{name}: must be a GPU tensor")
+        if not x.is_contiguous():
+            raise ValueError(f"{name}: must be contiguous")
+    dev = theta.device
+    if phi.device != dev:
+        raise ValueError(f"phi: on {phi.device}, expected {dev} (theta's device)")
+    (D, K), V = theta.shape, phi.shape[0]
+    if K < 1 or phi.shape[1] != K:
+        raise ValueError(f"theta / phi: row widths {K} and {phi.shape[1]} (one K >= 1)")
+    if not isinstance(doc, torch.Tensor) or doc.dim() != 1:
+        raise ValueError("doc: expected a 1-D tensor")
+    n = doc.numel()
+    if n >= 1 << 31:
+        raise ValueError(f"holdout_entries: {n} entries (n < 2^31)")
+    p_doc = _index("doc", doc, torch.int32, (n,), dev)
+    p_word = _index("word", word, torch.int32, (n,), dev)
+    p_t = _index("t", t, torch.int64, (n,), dev)
+    p_seen = _index("word_seen", word_seen, torch.uint8, (V,), dev)
+    # index bounds (host check before a gather kernel touches memory)
+    if n:
+        for name, idx, lim in (("doc", doc, D), ("word", word, V)):
+            if int(idx.max()) >= lim or int(idx.min()) < 0:
+                raise ValueError(f"{name}: index out of range")
+    ll = torch.empty(n, dtype=torch.float64, device=dev)
+    if n == 0:
+        return ll
+    lib().holdout_entries(theta.data_ptr(), phi.data_ptr(), int(K), p_doc, p_word, p_t, p_seen, int(n), ll.data_ptr(),
+                          int(max_blocks), _stream())
+    return ll
+
+
 def string_entropy(bytes_u8, offsets, max_blocks: int = 0):
     """float64 [n] Shannon entropy of the byte strings [offsets[i], offsets[i + 1]) of ``bytes_u8`` (uint8, on
     the GPU), bit for bit ``ops.reference.string_entropy`` (csrc/hip/string_entropy.hip).  ``offsets``: int64

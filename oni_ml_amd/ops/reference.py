@@ -427,3 +427,165 @@ def flow_words(hour, minute, second, port_a, port_b, ipkt, ibyt, time_cuts, ibyt
     spre = r2 | r3
     return dict(time=t, time_bin=nb(t, time_cuts), ibyt_bin=nb(ibyt, ibyt_cuts), ipkt_bin=nb(ipkt, ipkt_cuts),
                 word_port=wp, p_case=pc, src_prefix=spre.to(torch.int8), dst_prefix=dpre.to(torch.int8))
+
+
+# ---------------------------------------------------------------------------------------------- --holdout
+_M64 = (1 << 64) - 1
+
+
+def _as_i64(x: int) -> int:
+    """The 64 bits of a Python int as the signed value an int64 tensor holds."""
+    x &= _M64
+    return x - (1 << 64) if x >> 63 else x
+
+
+def splitmix64_int(x: int) -> int:
+    """csrc/common/splitmix64.h on a Python int (unsigned 64-bit)."""
+    x = (x + 0x9E3779B97F4A7C15) & _M64
+    x = ((x ^ (x >> 30)) * 0xBF58476D1CE4E5B9) & _M64
+    x = ((x ^ (x >> 27)) * 0x94D049BB133111EB) & _M64
+    return x ^ (x >> 31)
+
+
+def _lsr(x, n: int):
+    """Logical shift right of the 64 bits an int64 tensor holds."""
+    return (x >> n) & ((1 << (64 - n)) - 1)
+
+
+def splitmix64(x):
+    """csrc/common/splitmix64.h on an int64 tensor, bit for bit (the adds and products wrap, the shifts are
+    logical)."""
+    x = x + _as_i64(0x9E3779B97F4A7C15)
+    x = (x ^ _lsr(x, 30)) * _as_i64(0xBF58476D1CE4E5B9)
+    x = (x ^ _lsr(x, 27)) * _as_i64(0x94D049BB133111EB)
+    return x ^ _lsr(x, 31)
+
+
+def holdout_key(seed: int) -> int:
+    """The draw's key: splitmix64(seed ^ config.HOLDOUT_SALT), unsigned."""
+    from ..config import HOLDOUT_SALT
+    return splitmix64_int((int(seed) ^ HOLDOUT_SALT) & _M64)
+
+
+def holdout_thr(F: float) -> int:
+    """int(F * 2**53): exact (a double times a power of two), the integer the draw compares with."""
+    return int(float(F) * float(1 << 53))
+
+
+def check_holdout_draw(doc_ptr, counts, seed, thr):
+    """The value checks of ``holdout_draw`` (kernel wrapper and twin alike); host reads.  Returns the token total."""
+    import operator
+    operator.index(seed)
+    thr = operator.index(thr)
+    if not 0 < thr <= 1 << 52:
+        raise ValueError(f"holdout_draw: thr must be in (0, 2^52], got {thr}")
+    for name, x in (("doc_ptr", doc_ptr), ("counts", counts)):
+        if not isinstance(x, torch.Tensor) or x.dim() != 1 or x.dtype != torch.int64:
+            raise ValueError(f"{name}: expected a 1-D int64 tensor")
+        if not x.is_contiguous():
+            raise ValueError(f"{name}: must be contiguous")
+    if counts.device != doc_ptr.device:
+        raise ValueError(f"counts: on {counts.device}, expected {doc_ptr.device} (doc_ptr's device)")
+    nnz = counts.numel()
+    if nnz >= 1 << 31:
+        raise ValueError(f"holdout_draw: {nnz} entries (nnz < 2^31)")
+    if doc_ptr.numel() < 1 or int(doc_ptr[0]) != 0 or int(doc_ptr[-1]) != nnz:
+        raise ValueError("doc_ptr: must start at 0 and end at the number of entries")
+    if doc_ptr.numel() > 1 and int((doc_ptr[1:] - doc_ptr[:-1]).min()) < 0:
+        raise ValueError("doc_ptr: must be non-decreasing")
+    if nnz and int(counts.min()) < 0:
+        raise ValueError("counts: must be >= 0")
+    total = int(counts.sum()) if nnz else 0
+    if total >= 1 << 62:
+        raise ValueError(f"holdout_draw: {total} tokens (< 2^62)")
+    return total
+
+
+def holdout_rules(doc_ptr, counts, t, min_tokens=None):
+    """The two document rules on a raw draw ``t`` (int64 [nnz]), on any device, from int64 prefix sums and gathers
+    (``ops.sortgroup``): a document of fewer than ``config.HOLDOUT_MIN_TOKENS`` tokens is not split, and a document
+    all of whose tokens were drawn gets them all back -- t = 0 on all its entries either way."""
+    from ..config import HOLDOUT_MIN_TOKENS
+    from . import sortgroup as SG
+    mt = int(HOLDOUT_MIN_TOKENS if min_tokens is None else min_tokens)
+    nnz = counts.numel()
+    if nnz == 0:
+        return t
+    dev = counts.device
+
+    def doc_sums(x):
+        cs = torch.zeros(nnz + 1, dtype=torch.int64, device=dev)
+        cs[1:] = torch.cumsum(x, 0)
+        return SG.gather(cs, doc_ptr[1:]) - SG.gather(cs, doc_ptr[:-1])
+    d_all, d_out = doc_sums(counts), doc_sums(t)
+    split = (d_all >= mt) & (d_out < d_all)
+    doc_of = SG.segment_ids(doc_ptr[1:] - doc_ptr[:-1], total=nnz)
+    return torch.where(SG.gather(split, doc_of), t, torch.zeros_like(t))
+
+
+def holdout_draw(doc_ptr, counts, seed, thr, rules: bool = True, chunk: int = 1 << 22):
+    """Torch twin of ``ops.hip.holdout_draw`` (csrc/hip/holdout.hip) on any device, bit for bit: int64 [nnz], the
+    held-out tokens of every CSR entry.  Token j of entry e has the global index g = base[e] + j (base: the
+    exclusive prefix sum of ``counts``) and is held out iff ``splitmix64(key ^ g) >> 11 < thr`` with
+    ``key = holdout_key(seed)`` -- integers only.  ``rules``: then ``holdout_rules`` (False: the raw draw).
+    The tokens are walked ``chunk`` at a time."""
+    total = check_holdout_draw(doc_ptr, counts, seed, thr)
+    dev = counts.device
+    t = torch.zeros(counts.numel(), dtype=torch.int64, device=dev)
+    if total:
+        ends = torch.cumsum(counts, 0)
+        key = _as_i64(holdout_key(seed))
+        for a in range(0, total, int(chunk)):
+            g = torch.arange(a, min(total, a + int(chunk)), dtype=torch.int64, device=dev)
+            ent = torch.searchsorted(ends, g, right=True)      # the first entry that ends past g
+            hit = _lsr(splitmix64(g ^ key), 11) < int(thr)
+            t.index_add_(0, ent, hit.to(torch.int64))
+    return holdout_rules(doc_ptr, counts, t) if rules else t
+
+
+_LOG_RN_C = [2.0 / (2 * i + 3) for i in range(11)]
+_LOG_RN_LN2_HI = 6.93147180369123816490e-01
+_LOG_RN_LN2_LO = 1.90821492927058770002e-10
+
+
+def log_rn(y):
+    """Natural log of a positive float64 tensor from correctly rounded operations in a fixed order, the torch twin
+    of csrc/hip/holdout.hip ``log_rn`` bit for bit (within 2 ulp of ``numpy.log`` on [1e-300, 2]): frexp to
+    m in [0.5, 1) and e; m < sqrt(1/2): m doubled, e - 1; f = (m - 1) / (m + 1), s = f f; P by Horner over
+    c_i = 2 / (2 i + 3), i = 10 .. 0, a rounded product then a rounded sum per step; r = (f s) P + (f + f);
+    r = e ln2_lo + r; e ln2_hi + r."""
+    m, e = torch.frexp(y)
+    low = m < 0.70710678118654752
+    m = torch.where(low, m + m, m)
+    e = torch.where(low, e - 1, e)
+    f = (m - 1.0) / (m + 1.0)
+    s = f * f
+    P = torch.full_like(s, _LOG_RN_C[10])
+    for i in range(9, -1, -1):
+        P = P * s
+        P = P + _LOG_RN_C[i]
+    r = (f * s) * P + (f + f)
+    ed = e.to(torch.float64)
+    r = ed * _LOG_RN_LN2_LO + r
+    return ed * _LOG_RN_LN2_HI + r
+
+
+def holdout_entries(theta, phi, doc, word, t, word_seen, chunk: int = 1 << 20):
+    """Torch twin of ``ops.hip.holdout_entries`` (csrc/hip/holdout.hip) on any device, bit for bit: float64 [n],
+    ``t[e] * log_rn(theta[doc[e]] . phi[word[e]])`` for an entry with ``t[e] > 0`` whose word has a training entry
+    (``word_seen[word[e]] != 0``), else 0.0.  The dot is ``score``'s: a rounded product and a rounded sum per topic,
+    from 0.0."""
+    if theta.dim() != 2 or phi.dim() != 2 or theta.shape[1] != phi.shape[1] or theta.shape[1] < 1:
+        raise ValueError("holdout_entries: theta [D, K] and phi [V, K]")
+    n = doc.numel()
+    if word.numel() != n or t.numel() != n or word_seen.numel() != phi.shape[0]:
+        raise ValueError("holdout_entries: doc [n], word [n], t [n] and word_seen [V]")
+    K = int(theta.shape[1])
+    out = torch.zeros(n, dtype=torch.float64, device=theta.device)
+    for a in range(0, n, int(chunk)):
+        b = min(n, a + int(chunk))
+        d, w, tt = doc[a:b].long(), word[a:b].long(), t[a:b]
+        s = score(theta, phi, K, 0.0, d, w)[0]
+        use = (tt > 0) & (word_seen[w] != 0)
+        out[a:b] = torch.where(use, tt.to(torch.float64) * log_rn(s), torch.zeros_like(s))
+    return out

@@ -338,6 +338,147 @@ class Ensemble:
             self.R.emit(dict(stage=self.post + "_detail", ensemble_votes_hist=res["ensemble_votes_hist"]))
 
 
+# ------------------------------------------------------------------- --holdout
+# <LPATH>/holdout/: holdout.csv (a header and one line per evaluated K), holdout.json (the records, the split's
+# tallies, the selection and the key they were made under) and k<K>/, the model directory of K's training fit.
+HOLDOUT_CSV = ("topics", "em_iterations", "alpha", "train_likelihood", "heldout_tokens", "unseen_tokens",
+               "evaluated_tokens", "split_documents", "loglik", "loglik_per_token", "perplexity")
+
+
+def holdout_dir(lpath: str) -> str:
+    from ..config import HOLDOUT_DIR
+    return os.path.join(lpath, HOLDOUT_DIR)
+
+
+def holdout_key(cfg, size: dict) -> dict:
+    """What a holdout record was made under: a resume under another key is refused."""
+    return dict(fraction=float(cfg.holdout), topics=cfg.holdout_list(), seed=cfg.seed, alpha_init=cfg.alpha,
+                start=cfg.start, compat=cfg.compat, docs=size.get("docs"), terms=size.get("terms"), nnz=size.get("nnz"))
+
+
+def run_holdout(cfg, corpus: Corpus, device=None, log=print) -> dict:
+    """One split from ``cfg.seed``, then per K of the list, in list order: the training fit into
+    ``<LPATH>/holdout/k<K>/`` (only the 000 and final model files, no word assignments) and its held-out record.
+    A fit's model files are formatted on its writer threads while the next K fits.  Writes holdout.csv and
+    holdout.json; returns the json's content."""
+    import dataclasses
+    import shutil
+    import time
+
+    from ..models.lda import holdout as HO
+    hdir = holdout_dir(cfg.lpath)
+    shutil.rmtree(hdir, ignore_errors=True)
+    os.makedirs(hdir)
+    t0 = time.perf_counter()
+    train, t = HO.split(corpus, cfg.holdout, cfg.seed, device)
+    tallies = HO.split_tallies(corpus, train, t)
+    split_s = time.perf_counter() - t0
+    settings = dataclasses.replace(cfg.settings, lag=0)
+    records, pending = [], []
+    try:
+        for K in cfg.holdout_list():
+            res = estimate(train, K, cfg.alpha, settings, cfg.start, os.path.join(hdir, f"k{K}"), backend=cfg.backend,
+                           device=device, seed=cfg.seed, resume=False, write_word_assignments=False, verbose=False,
+                           defer_files=True)
+            pending.append(res.close_files)
+            fit = dict(topics=K, em_iterations=res.em_iterations, alpha=res.alpha, seconds=res.seconds,
+                       train_likelihood=res.likelihoods[-1][0] if res.likelihoods else None)
+            rec = HO.evaluate(corpus, train, t, res.gamma, res.log_beta, device, fit=fit)
+            res.engine = None
+            records.append(rec)
+            log(f"holdout: K = {K}: perplexity {rec['perplexity']} over {rec['evaluated_tokens']} held-out tokens "
+                f"({rec['unseen_tokens']} more on words unseen in training), {rec['em_iterations']} EM iterations, "
+                f"{rec['seconds']:.3f}s")
+    finally:
+        err = None
+        for close in pending:
+            try:
+                close()
+            except Exception as e:  # noqa: BLE001 -- the other fits' writers are still drained
+                err = err or e
+        if err is not None:
+            raise err
+    fmt = lambda v: "" if v is None else repr(v)      # noqa: E731 -- a float's repr reads back to the same bits
+    with open(os.path.join(hdir, "holdout.csv"), "w") as f:
+        f.write(",".join(HOLDOUT_CSV) + "\n")
+        for r in records:
+            f.write(",".join(fmt(r[k]) for k in HOLDOUT_CSV) + "\n")
+    size = dict(docs=corpus.num_docs, terms=corpus.num_terms, nnz=corpus.nnz)
+    out = dict(key=holdout_key(cfg, size), split=dict(tallies, seconds=split_s), records=records,
+               selected=HO.select(records))
+    save_json(os.path.join(hdir, "holdout.json"), out)
+    return out
+
+
+class Holdout:
+    """The --holdout part of a one-process pipeline; with ``cfg.holdout == 0`` every method does nothing.  Made
+    before any stage runs: a resume whose holdout stage is complete reads the record here -- a record made under
+    another key is refused -- and under --holdout-select sets ``cfg.topics`` to its selection, so that everything
+    after (the ensemble's member keys, the lda stage, the scorers) sees the selected K."""
+
+    def __init__(self, cfg, runner, device=None, log=print):
+        import shutil
+        self.cfg, self.R, self.device, self.log = cfg, runner, device, log
+        self.on = cfg.holdout > 0
+        self.record = None
+        if not cfg.resume:
+            shutil.rmtree(holdout_dir(cfg.lpath), ignore_errors=True)
+        if not (self.on and cfg.resume):
+            return
+        if runner.done("holdout") and not runner.done("lda_pre"):
+            runner.invalidate("holdout")      # the corpus is made again: so is its split
+        if runner.done("holdout"):
+            path = os.path.join(holdout_dir(cfg.lpath), "holdout.json")
+            try:
+                rec = load_json(path)
+            except (OSError, ValueError):
+                raise ValueError(f"--resume --holdout: the holdout stage is complete but {path} cannot be read; "
+                                 "run again from scratch") from None
+            key = holdout_key(cfg, runner.info("lda_pre"))
+            if rec.get("key") != json.loads(json.dumps(key)):
+                raise ValueError(f"--resume --holdout: {path} was made under {rec.get('key')}, this run asks for "
+                                 f"{key}; run again from scratch")
+            self.record = rec
+            self._select()
+        elif cfg.holdout_select and runner.done("lda"):
+            raise ValueError("--resume --holdout-select: the lda stage is complete but the holdout stage is not, so "
+                             "the model in LPATH was not fitted with a selected topic count; run again from scratch")
+
+    def _select(self):
+        if self.cfg.holdout_select:
+            k = self.record.get("selected")
+            if k is None:
+                raise ValueError("--holdout-select: no topic count was evaluated (no held-out token on a word seen in "
+                                 "training)")
+            self.cfg.topics = int(k)
+
+    def stage(self, corpus: Optional[Corpus], summary: dict, ens: Optional["Ensemble"] = None):
+        """Between lda_pre and lda: the holdout stage, or on a resume its record."""
+        if not self.on:
+            return
+        if self.record is None:
+            if corpus is None:
+                corpus = load_corpus_files(self.cfg.lpath)[0]
+            with self.R.stage("holdout") as res:
+                self.record = run_holdout(self.cfg, corpus, device=self.device, log=self.log)
+                res.update(selected=self.record["selected"], fits=len(self.record["records"]),
+                           heldout_tokens=self.record["split"]["heldout_tokens"])
+                self.R.emit(dict(stage="holdout_detail", **self.record))
+            before = self.cfg.topics
+            self._select()
+            if ens is not None and ens.on and self.cfg.resume and self.cfg.topics != before:
+                ens.fit = members_to_fit(self.cfg)      # the members' markers name their topic count
+        else:
+            self.R.skip("holdout")
+        recs = self.record["records"]
+        summary["holdout"] = dict(fraction=float(self.cfg.holdout), topics=[r["topics"] for r in recs],
+                                  perplexity=[r["perplexity"] for r in recs], selected=self.record["selected"],
+                                  select=bool(self.cfg.holdout_select), **{k: self.record["split"][k] for k in
+                                  ("heldout_tokens", "split_documents")},
+                                  unseen_tokens=[r["unseen_tokens"] for r in recs],
+                                  seconds=sum(r["seconds"] for r in recs) + self.record["split"]["seconds"])
+
+
 def strict_tables(mt: ModelTables, strict: bool = True) -> ModelTables:
     """θ/φ as the scorers see them after the text hand-off (Python-2 str -> toDouble).
 

@@ -1,5 +1,5 @@
-"""The stage sequence of the one-process pipelines (flow, dns, proxy): load -> <type>_pre -> lda_pre -> lda ->
-lda_post -> <type>_post.  A pipeline supplies a ``PipelineSpec`` (what it reads, how it featurizes, how it
+"""The stage sequence of the one-process pipelines (flow, dns, proxy): load -> <type>_pre -> lda_pre -> [holdout] ->
+lda -> lda_post -> <type>_post.  A pipeline supplies a ``PipelineSpec`` (what it reads, how it featurizes, how it
 scores); ``run_stages`` owns the rest: the runner and its resume rules, the corpus files, the lda stage, the
 model export, the ensemble, the scoring stage's summary and the deferred writers.  Imports no feature module."""
 from __future__ import annotations
@@ -83,7 +83,8 @@ def run_stages(cfg, spec: PipelineSpec, device=None, log=print) -> dict:
         if not os.path.exists(path):
             raise ValueError(f"--resume --explain: {path} is missing (lda_pre ran without --explain); "
                              "run again from scratch with --explain")
-    ens = C.Ensemble(cfg, R, post_stage, device, log)      # --ensemble; inert with one model
+    hold = C.Holdout(cfg, R, device, log)                  # --holdout; inert without it.  Ahead of the ensemble: a
+    ens = C.Ensemble(cfg, R, post_stage, device, log)      # resumed --holdout-select has set cfg.topics by now
     if need_pre or not R.done(post_stage):
         with R.stage("load") as res:
             inputs = spec.load(cfg, res, summary, log)
@@ -109,6 +110,7 @@ def run_stages(cfg, spec: PipelineSpec, device=None, log=print) -> dict:
         R.skip(pre_stage)
         R.skip("lda_pre")
 
+    hold.stage(corpus, summary, ens)      # --holdout: between lda_pre and lda; --holdout-select sets cfg.topics
     gamma = log_beta = None
     if not R.done("lda"):
         if corpus is None:
