@@ -213,6 +213,14 @@ PYBIND11_MODULE(_onihip, m) {
     oni::launch_explain_sides(a, max_blocks, S(stream));
   });
 
+  m.def("tail_theta_path", [](int R, int K) { return oni::tail_theta_path(R, K); });
+  m.def("tail_mass", [](u theta, u phi, int R, int K, int64_t V, u doc, u word, int64_t n, int64_t block,
+                        int64_t nblk, u scratch, u le, u tot, u rarer, u ties, int max_blocks, u stream) {
+    oni::TailArgs a{P<const double>(theta), P<const double>(phi), R, K, V, P<const int>(doc), P<const int>(word), n,
+                    block, nblk, P<double>(scratch), P<double>(le), P<double>(tot), P<int>(rarer), P<int>(ties)};
+    oni::launch_tail_mass(a, max_blocks, S(stream));
+  });
+
   m.def("holdout_draw", [](u base, u counts, u chunk_off, int64_t nnz, int64_t chunks, unsigned long long key,
                            unsigned long long thr, int lane_tokens, u t, int max_blocks, u stream) {
     oni::HoldoutDrawArgs a{P<const int64_t>(base), P<const int64_t>(counts), P<const int64_t>(chunk_off), nnz, chunks,

@@ -328,6 +328,36 @@ struct ExplainArgs {
 // max_blocks: cap on the workgroups (0: 8192)
 void launch_explain_sides(const ExplainArgs& a, int max_blocks, hipStream_t s);
 
+// --tail (tail_mass.hip).  For side i with doc[i] >= 0 and word[i] >= 0, over every row v of phi: p_v = the
+// side's score with row v in place of its word, as score_ensemble computes it; s = p_word.  The rows are cut into
+// nblk blocks of `block`; within a block, from 0.0 in row order, le_b += (p_v <= s ? p_v : 0.0) and tot_b += p_v;
+// the block values are added from 0.0 in block order.  rarer = #{p_v < s}, ties = #{p_v == s}.  Any other side:
+// NaN, NaN, -1, -1.  Plain rounded fp64 multiplies and adds, no atomics: the same bits for every grid.
+enum TailPath : int {
+  kTailRegisters = 0,   // theta row in registers (padded to a compiled width of at most 100 doubles)
+  kTailLdsTheta = 1,    // theta rows in LDS (R K <= 256)
+  kTailDirect = 2,      // rows read from global memory
+};
+struct TailArgs {
+  const double* theta;   // [D][R][K]
+  const double* phi;     // [V][R][K]
+  int R, K;              // 1 <= R <= kEnsembleMax, K >= 1
+  int64_t V;             // rows of phi, 0 <= V < 2^31
+  const int* doc;        // [n] theta row or -1 (bounds checked on the host)
+  const int* word;       // [n] phi row or -1
+  int64_t n;             // 0 <= n < 2^31
+  int64_t block;         // rows of a block, >= 1
+  int64_t nblk;          // ceil(V / block)
+  double* scratch;       // nblk * n * 24 bytes: [2][nblk][n] doubles (le_b, tot_b), then [2][nblk][n] ints
+  double* le;            // [n]
+  double* tot;           // [n]
+  int* rarer;            // [n]
+  int* ties;             // [n]
+};
+// max_blocks: cap on the workgroups per launch (0: 65536)
+void launch_tail_mass(const TailArgs& a, int max_blocks, hipStream_t s);
+int tail_theta_path(int R, int K);   // the TailPath the launch takes at this row shape
+
 // --holdout (holdout.hip).  holdout_draw: t[e] = the tokens j of CSR entry e, 0 <= j < counts[e], with
 // splitmix64(key ^ (base[e] + j)) >> 11 < thr -- integers only, so t depends on nothing but (key, thr, corpus).
 // An entry of at most lane_tokens tokens is drawn by one lane; a longer one is cut into chunks of

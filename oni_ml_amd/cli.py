@@ -92,11 +92,12 @@ def _apply_lda_args(a, st):
 
 def clean_workdir(lpath: str):
     """ml_ops.sh:53-54: remove stale *.dat,*.beta,*.gamma,*.other,*.pkl; keep *.csv (analyst feedback) -- except
-    what an earlier --explain run left, ``<type>_explain.csv`` and ``word_fields.npz``: a fresh run removes them
-    with or without the flag, since their lines would not describe this run's results file.  ``ensemble/`` and
-    ``holdout/`` (an earlier run's members, its held-out records and training fits) go too."""
+    what an earlier --explain or --tail run left, ``<type>_explain.csv``, ``word_fields.npz`` and
+    ``<type>_tail.csv``: a fresh run removes them with or without the flags, since their lines would not describe
+    this run's results file.  ``ensemble/`` and ``holdout/`` (an earlier run's members, its held-out records and
+    training fits) go too."""
     for pat in ("*.dat", "*.beta", "*.gamma", "*.other", "*.pkl", "checkpoint.npz", "final_model.npz",
-                "final_gamma.rank*.npz", "word_fields.npz", "*_explain.csv"):
+                "final_gamma.rank*.npz", "word_fields.npz", "*_explain.csv", "*_tail.csv"):
         for f in glob.glob(os.path.join(lpath, pat)):
             os.unlink(f)
     shutil.rmtree(os.path.join(lpath, ".stages"), ignore_errors=True)
@@ -121,6 +122,10 @@ def cmd_ml_ops(argv):
     ap.add_argument("--explain", action="store_true", default=None,
                     help="also write <type>_explain.csv: per written side the field of its word that makes it rare "
                          "and the conditional probability of every field (or EXPLAIN=1; one process only)")
+    ap.add_argument("--tail", action="store_true", default=None,
+                    help="also write <type>_tail.csv: per written side the share of its host's probability mass on "
+                         "words as rare as the event's or rarer, a p-value comparable across hosts (or TAIL=1; one "
+                         "process only)")
     ap.add_argument("--holdout", type=float, default=None, metavar="F",
                     help="hold the fraction F (0 < F <= 0.5) of every document's tokens out, fit on the rest and write "
                          "the held-out perplexity per topic count to <LPATH>/holdout/ (or HOLDOUT; one process only)")
@@ -180,7 +185,8 @@ def cmd_ml_ops(argv):
                            write_doc_wc=a.keep_doc_wc, word_assignments=a.word_assignments,
                            rank_gamma=a.rank_gamma, verbose=not a.quiet, cuts=a.cuts, hdfs=a.hdfs or None,
                            hadoop=a.hadoop, host_report=a.host_report, ensemble=a.ensemble, explain=a.explain,
-                           holdout=a.holdout, holdout_topics=a.holdout_topics, holdout_select=a.holdout_select)
+                           tail=a.tail, holdout=a.holdout, holdout_topics=a.holdout_topics,
+                           holdout_select=a.holdout_select)
     # --ensemble / ENSEMBLE (the site file and the environment set it too): refused here, before anything is
     # written and before a process group is asked for
     first = resolve(1)
@@ -188,6 +194,9 @@ def cmd_ml_ops(argv):
     # --explain / EXPLAIN likewise
     if first.explain and (a.gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1 or a.hdfs):
         raise ValueError(CFG.EXPLAIN_ONE_PROCESS)
+    # --tail / TAIL likewise
+    if first.tail and (a.gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1 or a.hdfs):
+        raise ValueError(CFG.TAIL_ONE_PROCESS)
     # --holdout / HOLDOUT likewise
     CFG.RunConfig.check_holdout(first.holdout, first.holdout_list(), first.holdout_select, a.start, a.compat, a.dsource,
                                 a.backend, a.gpus, a.hdfs, int(os.environ.get("WORLD_SIZE", "1")))

@@ -27,7 +27,7 @@ from .models.lda.settings import LDASettings
 
 ENV_KEYS = ("FLOW_PATH", "DNS_PATH", "PROXY_PATH", "HPATH", "LPATH", "LUSER", "TOL", "DUPFACTOR", "KRB_AUTH", "NODES",
             "UINODE", "RPATH", "LDAPATH", "SPK_EXEC", "SPK_EXEC_MEM", "TOP1M", "CUT", "MAXRESULTS", "ENSEMBLE", "EXPLAIN",
-            "HOLDOUT", "HOLDOUT_TOPICS")
+            "HOLDOUT", "HOLDOUT_TOPICS", "TAIL")
 
 # proxy has no multi-rank, sharded or HDFS-staged form
 PROXY_ONE_PROCESS = "proxy runs on one process: launch it without torchrun, with --gpus 1 and without --hdfs"
@@ -47,6 +47,15 @@ EXPLAIN_MAX_FIELDS = 8     # explained fields of a word space (csrc/hip/kernels.
 # block in member order, then the block sums in block order; the value is part of the result's bits
 GROUP_BLOCK = 256
 WORD_FIELDS = "word_fields.npz"      # <LPATH>/word_fields.npz: the vocabulary's keys and fields, under --explain
+
+# the tail file is made from one process's scored sides and its model tables: no multi-rank, sharded or HDFS-staged
+# form
+TAIL_ONE_PROCESS = "--tail runs on one process: launch it without torchrun, with --gpus 1 and without --hdfs"
+# rows of one vocabulary block of a tail sum (ops.hip / ops.reference tail_mass): a side's p_v are summed block by
+# block in row order, then the block sums in block order; the value is part of the result's bits, not a knob
+# (256 / 1024 / 4096 measured on an MI355X: profiles/tail_mass.md)
+TAIL_BLOCK = 1024
+TAIL_SCRATCH_MB = 256      # cap on the per-block partials of one launch of ops.hip.tail_mass; more sides: batches
 
 # --holdout: the split and the K fits are one process's: no multi-rank, sharded or HDFS-staged form
 HOLDOUT_ONE_PROCESS = "--holdout runs on one process: launch it without torchrun, with --gpus 1 and without --hdfs"
@@ -115,6 +124,8 @@ class RunConfig:
                                           # side under TOL, N >= 1: the N hosts with the lowest scores
     explain: bool = False                 # --explain / EXPLAIN: also write <type>_explain.csv, per written side the
                                           # field of its word that makes it rare
+    tail: bool = False                    # --tail / TAIL: also write <type>_tail.csv, per written side the host's
+                                          # probability mass at or below the event's word
     holdout: float = 0.0                  # --holdout / HOLDOUT: hold this fraction of every document's tokens out, fit
                                           # on the rest and report the held-out perplexity per topic count; 0: off
     holdout_topics: str = ""              # --holdout-topics / HOLDOUT_TOPICS: "K1,K2,..." to evaluate; "": topics alone
@@ -193,6 +204,8 @@ class RunConfig:
             raise ValueError(HOST_REPORT_ONE_PROCESS)
         if self.explain and (self.gpus > 1 or self.hdfs):
             raise ValueError(EXPLAIN_ONE_PROCESS)
+        if self.tail and (self.gpus > 1 or self.hdfs):
+            raise ValueError(TAIL_ONE_PROCESS)
         self.check_ensemble(self.ensemble, self.start, self.gpus, self.hdfs)
         self.check_holdout(self.holdout, self.holdout_list(), self.holdout_select, self.start, self.compat,
                            self.dsource, self.backend, self.gpus, self.hdfs)
@@ -304,6 +317,8 @@ def _apply(cfg: RunConfig, layer: Dict[str, object]):
         cfg.ensemble = int(layer["ENSEMBLE"])
     if "EXPLAIN" in layer and layer["EXPLAIN"] not in ("", None):
         cfg.explain = str(layer["EXPLAIN"]).strip().lower() not in ("0", "false", "no", "off")
+    if "TAIL" in layer and layer["TAIL"] not in ("", None):
+        cfg.tail = str(layer["TAIL"]).strip().lower() not in ("0", "false", "no", "off")
     if "HOLDOUT" in layer and layer["HOLDOUT"] not in ("", None):
         cfg.holdout = float(layer["HOLDOUT"])
     if "HOLDOUT_TOPICS" in layer and layer["HOLDOUT_TOPICS"] not in ("", None):

@@ -603,6 +603,88 @@ def explain_sides(theta, phi, gsum, doc, word, grow, dflt, max_blocks: int = 0):
     return cond, why
 
 
+TAIL_PATHS = ("registers", "lds_theta", "direct")
+
+
+def tail_theta_path(R: int, K: int) -> str:
+    """Which form of the tail kernel a row of R members x K topics takes (csrc/hip/tail_mass.hip): the theta row in
+    ``registers``, in LDS (``lds_theta``) or both rows read from global memory (``direct``)."""
+    return TAIL_PATHS[lib().tail_theta_path(int(R), int(K))]
+
+
+def tail_mass(theta, phi, doc, word, block=None, max_blocks: int = 0, scratch_mb=None):
+    """The host model's probability mass at or below a side's word (csrc/hip/tail_mass.hip;
+    ``ops.reference.tail_mass`` is the twin): ``(le float64 [n], tot float64 [n], rarer int32 [n], ties int32 [n])``
+    as new device tensors.
+
+    ``theta`` [D, R, K] / ``phi`` [V, R, K] as ``score_ensemble`` takes them, ``doc`` / ``word`` int32 [n] rows or
+    -1.  For a side with both rows, p_v is its ``score_ensemble`` score with phi row v in place of the word, s = p_w;
+    the V rows are cut into blocks of ``config.TAIL_BLOCK``; within a block, from 0.0 in row order,
+    ``le_b += p_v if p_v <= s else 0.0`` and ``tot_b += p_v``, and the block sums are added from 0.0 in block order:
+    plain rounded adds, no atomics, the same bits for every grid.  ``rarer`` / ``ties`` count ``p_v < s`` and
+    ``p_v == s``.  A side without a row gets NaN, NaN, -1, -1.  The tail probability is ``le / tot``.
+
+    The per-block partials (24 bytes per side and block) live in a scratch of at most ``scratch_mb`` MiB
+    (``config.TAIL_SCRATCH_MB``): more sides than fit are processed in batches.  Everything is checked on the host
+    before the launch; ``n == 0`` launches nothing.  ``max_blocks``: cap on the workgroups per launch (tests: a
+    small cap makes the grid-stride loops wrap).  ``block``: another block size (measurement:
+    scripts/tail_bench.py)."""
+    import operator
+    _max_blocks(max_blocks)
+    TB = operator.index(_CFG.TAIL_BLOCK if block is None else block)
+    if TB < 1:
+        raise ValueError(f"tail_mass: block must be >= 1, got {TB}")
+    cap_mb = float(_CFG.TAIL_SCRATCH_MB if scratch_mb is None else scratch_mb)
+    if not cap_mb > 0:
+        raise ValueError(f"tail_mass: scratch_mb must be > 0, got {scratch_mb!r}")
+    if not isinstance(theta, torch.Tensor) or theta.dim() != 3:
+        raise ValueError("theta: expected a [rows, R, K] tensor")
+    R, K = int(theta.shape[1]), int(theta.shape[2])
+    if not 1 <= R <= ENSEMBLE_MAX:
+        raise ValueError(f"tail_mass: R must be in [1, {ENSEMBLE_MAX}], got {R}")
+    if K < 1:
+        raise ValueError(f"tail_mass: K must be >= 1, got {K}")
+    _table3("theta", theta, R, K)
+    dev = theta.device
+    _table3("phi", phi, R, K, dev)
+    V = int(phi.shape[0])
+    if V >= 1 << 31 or TB >= 1 << 31:
+        raise ValueError(f"tail_mass: {V} phi rows, block {TB} (both < 2^31)")
+    if not isinstance(doc, torch.Tensor) or doc.dim() != 1:
+        raise ValueError("doc: expected a 1-D tensor")
+    n = doc.numel()
+    if n >= 1 << 31:
+        raise ValueError(f"tail_mass: {n} sides (n < 2^31)")
+    _index("doc", doc, torch.int32, (n,), dev)
+    _index("word", word, torch.int32, (n,), dev)
+    le = torch.empty(n, dtype=torch.float64, device=dev)
+    tot = torch.empty(n, dtype=torch.float64, device=dev)
+    rarer = torch.empty(n, dtype=torch.int32, device=dev)
+    ties = torch.empty(n, dtype=torch.int32, device=dev)
+    if n == 0:
+        return le, tot, rarer, ties
+    # index bounds (host check before a gather kernel touches memory)
+    for name, idx, lim in (("doc", doc, theta.shape[0]), ("word", word, V)):
+        if int(idx.max()) >= lim or int(idx.min()) < -1:
+            raise ValueError(f"{name}: index out of range")
+    L = lib()
+    if L.ensemble_max() != ENSEMBLE_MAX:
+        raise RuntimeError("tail_mass: config.ENSEMBLE_MAX differs from the compiled limit")
+    nblk = -(-V // TB)
+    per_side = 24 * max(nblk, 1)
+    batch = max(1, min(n, int(cap_mb * (1 << 20)) // per_side))
+    if batch < n and batch >= 256:
+        batch -= batch % 256      # whole tiles of sides
+    scratch = torch.empty(batch * max(nblk, 1) * 3, dtype=torch.float64, device=dev)
+    for s0 in range(0, n, batch):
+        m = min(batch, n - s0)
+        L.tail_mass(theta.data_ptr(), phi.data_ptr() if V else 0, R, K, V, doc.data_ptr() + 4 * s0,
+                    word.data_ptr() + 4 * s0, int(m), int(TB), int(nblk), scratch.data_ptr(), le.data_ptr() + 8 * s0,
+                    tot.data_ptr() + 8 * s0, rarer.data_ptr() + 4 * s0, ties.data_ptr() + 4 * s0, int(max_blocks),
+                    _stream())
+    return le, tot, rarer, ties
+
+
 def holdout_draw(doc_ptr, counts, seed, thr, max_blocks: int = 0, rules: bool = True, lane_tokens=None):
     """Held-out tokens of every CSR entry (csrc/hip/holdout.hip; ``ops.reference.holdout_draw`` is the twin): int64
     [nnz] as a new device tensor.

@@ -235,6 +235,81 @@ def explain_sides(theta, phi, gsum, doc, word, grow, dflt):
     return cond, why
 
 
+TAIL_SLAB = 1 << 22      # doubles of the [sides, V] slab the tail twin holds at a time
+
+
+def tail_mass(theta, phi, doc, word, block=None, slab: int = TAIL_SLAB):
+    """Torch twin of ``ops.hip.tail_mass`` (csrc/hip/tail_mass.hip) on any device, bit for bit, and the CPU
+    pipeline's path: ``(le float64 [n], tot float64 [n], rarer int32 [n], ties int32 [n])``.  ``theta`` [D, R, K],
+    ``phi`` [V, R, K]; ``doc`` / ``word`` [n] rows or -1.  For a side with both rows, p_v is its ``score_ensemble``
+    score with phi row v in place of the word and s = p_w; the V rows are cut into blocks of ``block``
+    (``config.TAIL_BLOCK``); within a block, from 0.0 in row order, ``le_b += p_v if p_v <= s else 0.0`` and
+    ``tot_b += p_v``; the block sums are added from 0.0 in block order -- plain rounded adds.  (A row that the last
+    block does not have adds +0.0, which changes no bit of a sum that started at +0.0.)  ``rarer`` / ``ties`` count
+    ``p_v < s`` and ``p_v == s``; a NaN p_v enters neither count, enters ``le`` as 0.0 and makes ``tot`` NaN.  A
+    side without a row gets NaN, NaN, -1, -1.  Sides are taken in batches of at most ``slab`` / V: the loops run
+    over topic, then block position, then block."""
+    from ..config import TAIL_BLOCK
+    TB = int(TAIL_BLOCK if block is None else block)
+    if TB < 1:
+        raise ValueError(f"tail_mass: block must be >= 1, got {TB}")
+    if theta.dim() != 3 or phi.dim() != 3 or theta.shape[1:] != phi.shape[1:] or theta.dtype != torch.float64 \
+            or phi.dtype != torch.float64:
+        raise ValueError("tail_mass: theta [D, R, K] and phi [V, R, K] float64")
+    doc, word = doc.reshape(-1).to(torch.int64), word.reshape(-1).to(torch.int64)
+    if doc.numel() != word.numel():
+        raise ValueError("tail_mass: doc [n] and word [n]")
+    V, R, K = phi.shape
+    n = doc.numel()
+    dev = theta.device
+    le = torch.full((n,), float("nan"), dtype=torch.float64, device=dev)
+    tot = torch.full((n,), float("nan"), dtype=torch.float64, device=dev)
+    rarer = torch.full((n,), -1, dtype=torch.int32, device=dev)
+    ties = torch.full((n,), -1, dtype=torch.int32, device=dev)
+    if n == 0:
+        return le, tot, rarer, ties
+    if int(doc.max()) >= theta.shape[0] or int(doc.min()) < -1 or int(word.max()) >= V or int(word.min()) < -1:
+        raise ValueError("tail_mass: doc or word out of range")
+    have = torch.nonzero((doc >= 0) & (word >= 0)).reshape(-1)
+    nblk = -(-V // TB)
+    pad = nblk * TB - V
+    zero = torch.zeros((), dtype=torch.float64, device=dev)
+    step = max(1, int(slab) // max(V, 1))
+    for b0 in range(0, have.numel(), step):
+        rows = have[b0:b0 + step]
+        th = theta[doc[rows]]                                           # [m, R, K]
+        m = rows.numel()
+        p = torch.zeros((m, V), dtype=torch.float64, device=dev)
+        for r in range(R):
+            acc = torch.zeros((m, V), dtype=torch.float64, device=dev)
+            for k in range(K):
+                acc = acc + th[:, r, k].unsqueeze(1) * phi[:, r, k].unsqueeze(0)      # rounded product, rounded sum
+            p = p + acc
+        if R != 1:      # x / 1.0 is x
+            p = p / float(R)
+        s = torch.gather(p, 1, word[rows].unsqueeze(1))                 # [m, 1]: p_w, so w counts itself
+        rarer[rows] = (p < s).sum(1).to(torch.int32)
+        ties[rows] = (p == s).sum(1).to(torch.int32)
+        sel = torch.where(p <= s, p, zero)
+        if pad:
+            fill = torch.zeros((m, pad), dtype=torch.float64, device=dev)
+            p, sel = torch.cat([p, fill], 1), torch.cat([sel, fill], 1)
+        p, sel = p.reshape(m, nblk, TB), sel.reshape(m, nblk, TB)
+        le_b = torch.zeros((m, nblk), dtype=torch.float64, device=dev)
+        tot_b = torch.zeros((m, nblk), dtype=torch.float64, device=dev)
+        for j in range(min(TB, V)):      # (one block: the positions past V hold the +0.0 of the padding)
+            le_b = le_b + sel[:, :, j]
+            tot_b = tot_b + p[:, :, j]
+        le_s = torch.zeros(m, dtype=torch.float64, device=dev)
+        tot_s = torch.zeros(m, dtype=torch.float64, device=dev)
+        for b in range(nblk):
+            le_s = le_s + le_b[:, b]
+            tot_s = tot_s + tot_b[:, b]
+        le[rows] = le_s
+        tot[rows] = tot_s
+    return le, tot, rarer, ties
+
+
 def select_lowest(key, flag, limit, with_count: bool = False):
     """Torch twin of ``ops.hip.select_lowest`` (csrc/hip/select_lowest.hip) on any device: the row indices
     (int64, ascending) of the ``limit`` flagged rows that a stable ascending sort of their keys puts first, all

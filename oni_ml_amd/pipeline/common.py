@@ -575,7 +575,7 @@ def write_host_report(cfg, tables: ModelTables, doc_a, score_a, doc_b, score_b, 
 
 @dataclass
 class ExplainInput:
-    """What a scorer hands ``write_results`` for --explain, per side of an event (flow: source, destination):
+    """What a scorer hands ``write_results`` for --explain and --tail, per side of an event (flow: source, destination):
     ``words`` the φ row of every event's side (-1: none), ``ips`` the (names, id of every event) of the side's
     document, ``cols`` the positions (word, score) of the side's columns in the scorer's ``row_cols`` list."""
     model: object
@@ -661,6 +661,72 @@ def write_explain(cfg, tables, order, key, sides, ex: ExplainInput, cols, sep: s
                 explain_max_group=dict(zip(names, (int(x) for x in largest))))
 
 
+TAIL_DECADES = ("<1e-6", "<1e-5", "<1e-4", "<1e-3", "<1e-2", "<1e-1", "<=1")
+
+
+def write_tail(cfg, tables, order, key, sides, ex: ExplainInput, cols, sep: str = ",", log=print) -> dict:
+    """--tail: ``<type>_tail.csv`` next to the results file, line i describing its line i (``order``: the written
+    events; ``cols``: their ``row_cols``): the key score, then per side the document, the word, the side's score,
+    ``tail`` and ``rarer``.  ``tail`` is the share of the document's probability mass -- over the scorer's whole φ
+    table -- on the words whose score at this document is at most the side's (``scorer.tail_mass``: le / tot, one
+    rounded division), ``rarer`` the number of words that score strictly lower; both empty for a side without a
+    θ or a φ row.  The values depend on the pair (document, word) only: the distinct pairs of the written sides are
+    evaluated and gathered.  Returns the summary entries."""
+    from ..ops import native
+    from ..ops import sortgroup as SG
+    from ..score import scorer as S
+    dev = key.device
+    n = int(order.size)
+    o_t = torch.from_numpy(order).to(dev)
+    n_sides = len(ex.words)
+    theta, phi = S.model_tables3(ex.model)
+    V, R, K = (int(x) for x in phi.shape)
+    tail = np.full(n_sides * n, np.nan)
+    rarer = np.full(n_sides * n, -1, np.int64)
+    pairs, tot_range = 0, None
+    if n:
+        doc = torch.cat([SG.gather(sides[2 * j], o_t).to(torch.int64) for j in range(n_sides)])
+        word = torch.cat([SG.gather(w, o_t).to(torch.int64) for w in ex.words])
+        ok = (doc >= 0) & (word >= 0)
+        pk, inv = SG.unique(torch.where(ok, doc * V + word, torch.full_like(doc, -1)), return_inverse=True)
+        none = int(pk[0] < 0)      # the -1 of the sides without a pair sorts first
+        pk = pk[none:]
+        pairs = int(pk.numel())
+        if pairs:
+            le, tot, rr, _ = S.tail_mass(ex.model, pk // V, pk % V)
+            at = (inv - none).clamp_min(0)
+            ok_h = ok.cpu().numpy()
+            with np.errstate(invalid="ignore", divide="ignore"):
+                t_u = le.cpu().numpy() / tot.cpu().numpy()      # one rounded division
+            at_h = at.cpu().numpy()
+            tail = np.where(ok_h, t_u[at_h], np.nan)
+            rarer = np.where(ok_h, rr.cpu().numpy().astype(np.int64)[at_h], -1)
+            tot_range = [float(tot.min()), float(tot.max())]
+    out_cols = [("java", SG.gather(key, o_t).cpu().numpy())]
+    for j in range(n_sides):
+        ip_names, ip_ids = ex.ips[j]
+        t, r = tail[j * n:(j + 1) * n], rarer[j * n:(j + 1) * n]
+        have = ~np.isnan(t)
+        text = native.lib().java_double_array(np.ascontiguousarray(t[have], np.float64))
+        idx = np.full(n, -1, np.int32)
+        idx[have] = np.arange(len(text), dtype=np.int32)
+        ur, r_inv = np.unique(r[r >= 0], return_inverse=True)
+        r_idx = np.full(n, -1, np.int32)
+        r_idx[r >= 0] = r_inv.astype(np.int32)
+        out_cols += [("dict", ip_names, SG.gather(ip_ids, o_t).cpu().numpy().astype(np.int32)),
+                     cols[ex.cols[j][0]], cols[ex.cols[j][1]], ("dict", text, idx),
+                     ("dict", [str(int(x)) for x in ur], r_idx)]
+    out = os.path.join(cfg.lpath, f"{cfg.dsource}_tail.csv")
+    native.lib().write_rows(out, None, out_cols, sep=sep, threads=cfg.threads, n=n)
+    good = tail[~np.isnan(tail)]
+    edges = np.asarray([1e-6, 1e-5, 1e-4, 1e-3, 1e-2, 1e-1])
+    hist = np.bincount(np.searchsorted(edges, good, side="right"), minlength=len(TAIL_DECADES)).astype(np.int64)
+    log(f"{cfg.dsource}_post: {n_sides * n} sides placed in {out} "
+        f"({pairs} pairs x {V} words x {K} topics x {R} members)")
+    return dict(tail_words=V, tail_pairs=pairs, tail_total_range=tot_range,
+                tail_hist=dict(zip(TAIL_DECADES + ("none",), hist.tolist() + [int(tail.size - good.size)])))
+
+
 def one_sided_index(tables, ip_names, ip, unames, inv, device, ip_map=None):
     """The one-sided scorers' (dns, proxy) index set-up: (θ, φ, θ row of every event, φ row of every event).
     ``ip`` / ``inv``: every event's id into ``ip_names`` / ``unames``; ``ip_map``: the doc row of every ip id
@@ -697,7 +763,7 @@ def write_results(cfg, tables, what: str, ranked, key, row_cols, events: int, si
     ``doc_a, score_a, doc_b, score_b`` of ``write_host_report``) and the votes histogram.  Several ranks
     (``ctx``): the ranks' rows merged into one ascending file (``shardio.merge_sorted_rows``, the sortByKey
     shuffle), the counts summed.  ``extra``: further result entries.  ``explain``: the sides' φ rows and columns
-    for ``write_explain`` (one process, under --explain)."""
+    for ``write_explain`` and ``write_tail`` (one process, under --explain / --tail)."""
     from ..ops import native
     order, below, limit = ranked
     n = int(order.size)
@@ -717,8 +783,9 @@ def write_results(cfg, tables, what: str, ranked, key, row_cols, events: int, si
     log(f"{cfg.dsource}_post: {flagged_text(n, below, limit, what, cfg.tol)} written to {out}")
     hosts = write_host_report(cfg, tables, *sides, row_cols, sep=sep, log=log) if cfg.host_report else {}
     why = write_explain(cfg, tables, order, key, sides, explain, cols, sep=sep, log=log) if cfg.explain else {}
+    tail = write_tail(cfg, tables, order, key, sides, explain, cols, sep=sep, log=log) if cfg.tail else {}
     return dict(flagged=n, below_tol=below, events=events, **(extra or {}), **hosts,
-                **votes_hist(votes, order, cfg.ensemble), **why)
+                **votes_hist(votes, order, cfg.ensemble), **why, **tail)
 
 
 def save_json(path: str, obj):

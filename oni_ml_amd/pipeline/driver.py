@@ -164,6 +164,10 @@ def run_stages(cfg, spec: PipelineSpec, device=None, log=print) -> dict:
                     why = {k: res[k] for k in ("explain_fields", "explain_why_hist", "explain_max_group")}
                     summary.update(why)
                     R.emit(dict(stage=post_stage + "_detail", **why))
+                if cfg.tail:
+                    tail = {k: res[k] for k in ("tail_words", "tail_pairs", "tail_hist", "tail_total_range")}
+                    summary.update(tail)
+                    R.emit(dict(stage=post_stage + "_detail", **tail))
         else:
             R.skip(post_stage)
     except BaseException:

@@ -244,6 +244,21 @@ def explain_sides(model, gsum: torch.Tensor, doc: torch.Tensor, word: torch.Tens
     return fn(theta.contiguous(), phi.contiguous(), gsum.contiguous(), i32(doc), i32(word), i32(grow), model.default)
 
 
+def tail_mass(model, doc: torch.Tensor, word: torch.Tensor):
+    """``(le, tot float64 [n]; rarer, ties int32 [n])`` of the sides: the model's probability mass on the words
+    that are as rare at the side's document as its word, or rarer, the mass of the whole table, and the counts of
+    rarer and equally rare words (``ops.hip.tail_mass`` on the GPU, its torch twin elsewhere: the same bits).
+    ``model``: a TopicModel (one member through a ``[rows, 1, K]`` view) or an EnsembleModel; ``doc`` / ``word``: θ /
+    φ rows or -1."""
+    theta, phi = model_tables3(model)
+    i32 = lambda t: t.to(torch.int32).contiguous()      # noqa: E731
+    if theta.device.type == "cuda":
+        from ..ops.hip import tail_mass as fn
+    else:
+        from ..ops.reference import tail_mass as fn
+    return fn(theta.contiguous(), phi.contiguous(), i32(doc), i32(word))
+
+
 def rank_hosts(min_score: torch.Tensor, flagged: torch.Tensor, limit: Optional[int] = None) -> np.ndarray:
     """Document rows with at least one flagged side, ascending by their lowest score, ties to the lowest row
     (int64 host array); ``limit``: only the first ``limit`` of them (the MAXRESULTS radix select and its tie
