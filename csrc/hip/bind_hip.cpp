@@ -220,6 +220,12 @@ PYBIND11_MODULE(_onihip, m) {
                     block, nblk, P<double>(scratch), P<double>(le), P<double>(tot), P<int>(rarer), P<int>(ties)};
     oni::launch_tail_mass(a, max_blocks, S(stream));
   });
+  m.def("tail_mass_docs", [](u theta, u phi, int R, int K, int64_t V, u doc, u word, int64_t n, int64_t block,
+                             int64_t nblk, u scratch, u le, u tot, u rarer, u ties, int max_blocks, u stream) {
+    oni::TailArgs a{P<const double>(theta), P<const double>(phi), R, K, V, P<const int>(doc), P<const int>(word), n,
+                    block, nblk, P<double>(scratch), P<double>(le), P<double>(tot), P<int>(rarer), P<int>(ties)};
+    oni::launch_tail_docs(a, max_blocks, S(stream));
+  });
 
   m.def("holdout_draw", [](u base, u counts, u chunk_off, int64_t nnz, int64_t chunks, unsigned long long key,
                            unsigned long long thr, int lane_tokens, u t, int max_blocks, u stream) {

@@ -357,6 +357,10 @@ struct TailArgs {
 // max_blocks: cap on the workgroups per launch (0: 65536)
 void launch_tail_mass(const TailArgs& a, int max_blocks, hipStream_t s);
 int tail_theta_path(int R, int K);   // the TailPath the launch takes at this row shape
+// --tail-tol (tail_docs.hip): the same four values, bit for bit, for pairs sorted by document -- doc non-decreasing,
+// doc >= 0 and word >= 0 (checked on the host) -- with p_v evaluated once per (document of a tile of 256 pairs,
+// row) instead of once per pair.  Only where tail_theta_path(R, K) == kTailRegisters; any other width throws.
+void launch_tail_docs(const TailArgs& a, int max_blocks, hipStream_t s);
 
 // --holdout (holdout.hip).  holdout_draw: t[e] = the tokens j of CSR entry e, 0 <= j < counts[e], with
 // splitmix64(key ^ (base[e] + j)) >> 11 < thr -- integers only, so t depends on nothing but (key, thr, corpus).

@@ -35,84 +35,20 @@
 
 #include "common.h"
 #include "kernels.h"
+#include "tail_common.h"
 
 namespace oni {
 
 namespace {
 
-constexpr int kThreads = 256;
+using namespace tail;   // Part, take, dot_any, dot_pad, stage_rows, put, reg_topics: shared with tail_docs.hip
+
 constexpr int kPhiLds = 4096;        // doubles of staged phi rows, register form (32 KiB)
-constexpr int kRegMax = 100;         // doubles of a padded theta row in registers
 constexpr int kGenMax = 256;         // widest row (R K) of the LDS-theta form
 constexpr int kGenSides = 64;        // sides of its tile, one per lane of a wave
 constexpr int kGenWaves = kThreads / kGenSides;   // vocabulary blocks a workgroup walks at a time
 constexpr int kGenTheta = kGenSides * kGenMax;    // doubles of theta rows in LDS (128 KiB)
 constexpr int kGenPhi = 512;         // doubles of staged phi rows per wave (4 x 4 KiB)
-
-struct Part {
-  double le, tot;
-  int rarer, ties;
-};
-
-__device__ __forceinline__ void take(Part& a, double p, double s) {
-  // a select, then a plain rounded add: no branch in the sum.  A NaN p compares false everywhere.
-  const double sel = p <= s ? p : 0.0;
-  a.le = a.le + sel;
-  a.tot = a.tot + p;
-  a.rarer += p < s ? 1 : 0;
-  a.ties += p == s ? 1 : 0;
-}
-
-// the scorers' member dots over rows of any width; th advances by `ts` doubles per element
-__device__ __forceinline__ double dot_any(const double* __restrict__ th, int ts, const double* __restrict__ p, int R,
-                                          int K, double rd) {
-#pragma clang fp contract(off)
-  double sum = 0.0;
-  for (int r = 0; r < R; ++r) {
-    double acc = 0.0;
-#pragma unroll 4
-    for (int k = 0; k < K; ++k) {
-      const double prod = th[(size_t)(r * K + k) * ts] * p[r * K + k];   // rounded product, then rounded sum
-      acc = acc + prod;
-    }
-    sum = sum + acc;
-  }
-  return R == 1 ? sum : sum / rd;   // x / 1.0 is x
-}
-
-// the same over padded rows: th in registers [TM][TK], p in LDS [TM][TK], 0.0 in the padding of both
-template <int TK, int TM>
-__device__ __forceinline__ double dot_pad(const double (&th)[TK * TM], const double2* __restrict__ p, int R,
-                                          double rd) {
-#pragma clang fp contract(off)
-  double sum = 0.0;
-#pragma unroll
-  for (int m = 0; m < TM; ++m) {
-    if (m < R) {   // uniform; a member past R would add +0.0
-      double acc = 0.0;
-#pragma unroll
-      for (int k = 0; k < TK; k += 2) {
-        const double2 q = p[(m * TK + k) / 2];
-        const double p0 = th[m * TK + k] * q.x;
-        acc = acc + p0;
-        const double p1 = th[m * TK + k + 1] * q.y;
-        acc = acc + p1;
-      }
-      sum = sum + acc;
-    }
-  }
-  return R == 1 ? sum : sum / rd;
-}
-
-__device__ __forceinline__ void put(const TailArgs& a, int64_t b, int64_t i, const Part& pt) {
-  const size_t cells = (size_t)a.nblk * (size_t)a.n, at = (size_t)b * (size_t)a.n + (size_t)i;
-  double* sd = a.scratch;
-  int* si = reinterpret_cast<int*>(sd + 2 * cells);
-  sd[at] = pt.le;
-  sd[cells + at] = pt.tot;
-  si[at] = pt.rarer;
-  si[cells + at] = pt.ties;
-}
 
 // registers: theta row padded in registers, phi sub-tiles padded in LDS
 template <int TK, int TM>
@@ -139,18 +75,7 @@ __global__ __launch_bounds__(kThreads) void tail_blocks_reg_kernel(TailArgs a, i
     for (int64_t r0 = v0; r0 < v1; r0 += sub) {
       const int nr = (int)(v1 - r0 < sub ? v1 - r0 : sub);
       __syncthreads();   // the lanes are done with the previous sub-tile
-      double* dst = reinterpret_cast<double*>(ph_l);
-      for (int t = threadIdx.x; t < nr * R; t += kThreads) {   // one (row, member) run per lane
-        const int row = t / R, m = t % R;
-        const double* src = a.phi + (size_t)(r0 + row) * RK + (size_t)m * K;
-        double* to = dst + row * rowl + m * TK;
-        if (vec) {   // K even, phi 16-byte aligned: so is every member run
-          for (int k = 0; k < K / 2; ++k) reinterpret_cast<double2*>(to)[k] = reinterpret_cast<const double2*>(src)[k];
-        } else {
-          for (int k = 0; k < K; ++k) to[k] = src[k];
-        }
-        for (int k = K; k < TK; ++k) to[k] = 0.0;
-      }
+      stage_rows(reinterpret_cast<double*>(ph_l), rowl, a.phi, r0, nr, R, K, TK, vec);
       __syncthreads();
       if (ok) {
         if (W <= 50) {   // two rows in flight where the registers allow it
@@ -257,15 +182,6 @@ __global__ __launch_bounds__(kThreads) void tail_fold_kernel(TailArgs a) {
   }
 }
 
-constexpr int kLadder[] = {4, 8, 20, 32, 50, 100};
-
-// padded topics of the register form, 0 when the row does not fit it
-int reg_topics(int R, int K) {
-  for (int tk : kLadder)
-    if (K <= tk) return R == 1 || R <= kRegMax / tk ? tk : 0;
-  return 0;
-}
-
 template <int TK>
 void launch_reg(const TailArgs& a, int64_t ntiles, int vec, unsigned blocks, hipStream_t s) {
   constexpr int TM = kRegMax / TK;
@@ -283,19 +199,32 @@ int tail_theta_path(int R, int K) {
   return (int64_t)R * K <= kGenMax ? kTailLdsTheta : kTailDirect;
 }
 
-void launch_tail_mass(const TailArgs& a, int max_blocks, hipStream_t s) {
+bool tail_args_check(const TailArgs& a, int max_blocks, const char* who) {
+  const std::string w(who);
   if (a.n < 0 || a.n >= ((int64_t)1 << 31) || a.V < 0 || a.V >= ((int64_t)1 << 31))
-    throw std::runtime_error("tail_mass: n or V outside 0 .. 2^31 - 1");
-  if (a.R < 1 || a.R > kEnsembleMax) throw std::runtime_error("tail_mass: R outside 1 .. " + std::to_string(kEnsembleMax));
-  if (a.K < 1 || (int64_t)a.R * a.K >= ((int64_t)1 << 31)) throw std::runtime_error("tail_mass: K < 1 or R K >= 2^31");
-  if (a.block < 1 || a.block >= ((int64_t)1 << 31)) throw std::runtime_error("tail_mass: block outside 1 .. 2^31 - 1");
-  if (a.nblk != (a.V + a.block - 1) / a.block) throw std::runtime_error("tail_mass: nblk is not ceil(V / block)");
-  if (max_blocks < 0) throw std::runtime_error("tail_mass: max_blocks < 0");
-  if (a.n == 0) return;
+    throw std::runtime_error(w + ": n or V outside 0 .. 2^31 - 1");
+  if (a.R < 1 || a.R > kEnsembleMax) throw std::runtime_error(w + ": R outside 1 .. " + std::to_string(kEnsembleMax));
+  if (a.K < 1 || (int64_t)a.R * a.K >= ((int64_t)1 << 31)) throw std::runtime_error(w + ": K < 1 or R K >= 2^31");
+  if (a.block < 1 || a.block >= ((int64_t)1 << 31)) throw std::runtime_error(w + ": block outside 1 .. 2^31 - 1");
+  if (a.nblk != (a.V + a.block - 1) / a.block) throw std::runtime_error(w + ": nblk is not ceil(V / block)");
+  if (max_blocks < 0) throw std::runtime_error(w + ": max_blocks < 0");
+  if (a.n == 0) return false;
   if (!a.theta || !a.doc || !a.word || !a.le || !a.tot || !a.rarer || !a.ties)
-    throw std::runtime_error("tail_mass: null buffer");
-  if (a.V > 0 && (!a.phi || !a.scratch)) throw std::runtime_error("tail_mass: null buffer");
-  if ((uintptr_t)a.scratch % 8 != 0) throw std::runtime_error("tail_mass: scratch is not 8-byte aligned");
+    throw std::runtime_error(w + ": null buffer");
+  if (a.V > 0 && (!a.phi || !a.scratch)) throw std::runtime_error(w + ": null buffer");
+  if ((uintptr_t)a.scratch % 8 != 0) throw std::runtime_error(w + ": scratch is not 8-byte aligned");
+  return true;
+}
+
+void launch_tail_fold(const TailArgs& a, int64_t cap, hipStream_t s) {
+  int64_t blocks = (a.n + kThreads - 1) / kThreads;
+  if (blocks > cap) blocks = cap;
+  hipLaunchKernelGGL(tail_fold_kernel, dim3((unsigned)blocks), dim3(kThreads), 0, s, a);
+  ONI_HIP_CHECK(hipGetLastError());
+}
+
+void launch_tail_mass(const TailArgs& a, int max_blocks, hipStream_t s) {
+  if (!tail_args_check(a, max_blocks, "tail_mass")) return;
   const int64_t cap = max_blocks > 0 ? max_blocks : 65536;
   if (a.nblk > 0) {
     const int path = tail_theta_path(a.R, a.K);
@@ -323,10 +252,7 @@ void launch_tail_mass(const TailArgs& a, int max_blocks, hipStream_t s) {
     }
     ONI_HIP_CHECK(hipGetLastError());
   }
-  int64_t blocks = (a.n + kThreads - 1) / kThreads;
-  if (blocks > cap) blocks = cap;
-  hipLaunchKernelGGL(tail_fold_kernel, dim3((unsigned)blocks), dim3(kThreads), 0, s, a);
-  ONI_HIP_CHECK(hipGetLastError());
+  launch_tail_fold(a, cap, s);
 }
 
 }  // namespace oni

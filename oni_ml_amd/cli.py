@@ -126,6 +126,11 @@ def cmd_ml_ops(argv):
                     help="also write <type>_tail.csv: per written side the share of its host's probability mass on "
                          "words as rare as the event's or rarer, a p-value comparable across hosts (or TAIL=1; one "
                          "process only)")
+    ap.add_argument("--tail-tol", type=float, default=None, metavar="P",
+                    help="flag and rank the events by their tail p-value instead of the score: an event is written "
+                         "when the lower of its sides' tails is < P (0 < P <= 1), ascending by it; TOL takes no part. "
+                         "Implies --tail.  The tail of every distinct (host, word) pair of the day is evaluated, "
+                         "hosts x words x topics x members multiply-adds with no cap (or TAIL_TOL; one process only)")
     ap.add_argument("--holdout", type=float, default=None, metavar="F",
                     help="hold the fraction F (0 < F <= 0.5) of every document's tokens out, fit on the rest and write "
                          "the held-out perplexity per topic count to <LPATH>/holdout/ (or HOLDOUT; one process only)")
@@ -185,7 +190,7 @@ def cmd_ml_ops(argv):
                            write_doc_wc=a.keep_doc_wc, word_assignments=a.word_assignments,
                            rank_gamma=a.rank_gamma, verbose=not a.quiet, cuts=a.cuts, hdfs=a.hdfs or None,
                            hadoop=a.hadoop, host_report=a.host_report, ensemble=a.ensemble, explain=a.explain,
-                           tail=a.tail, holdout=a.holdout, holdout_topics=a.holdout_topics,
+                           tail=a.tail, tail_tol=a.tail_tol, holdout=a.holdout, holdout_topics=a.holdout_topics,
                            holdout_select=a.holdout_select)
     # --ensemble / ENSEMBLE (the site file and the environment set it too): refused here, before anything is
     # written and before a process group is asked for
@@ -194,8 +199,10 @@ def cmd_ml_ops(argv):
     # --explain / EXPLAIN likewise
     if first.explain and (a.gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1 or a.hdfs):
         raise ValueError(CFG.EXPLAIN_ONE_PROCESS)
-    # --tail / TAIL likewise
-    if first.tail and (a.gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1 or a.hdfs):
+    # --tail / TAIL and --tail-tol / TAIL_TOL likewise
+    if first.tail_tol is not None:
+        CFG.RunConfig.check_tail_tol(first.tail_tol)
+    if (first.tail or first.tail_tol is not None) and (a.gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1 or a.hdfs):
         raise ValueError(CFG.TAIL_ONE_PROCESS)
     # --holdout / HOLDOUT likewise
     CFG.RunConfig.check_holdout(first.holdout, first.holdout_list(), first.holdout_select, a.start, a.compat, a.dsource,

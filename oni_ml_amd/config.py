@@ -27,7 +27,7 @@ from .models.lda.settings import LDASettings
 
 ENV_KEYS = ("FLOW_PATH", "DNS_PATH", "PROXY_PATH", "HPATH", "LPATH", "LUSER", "TOL", "DUPFACTOR", "KRB_AUTH", "NODES",
             "UINODE", "RPATH", "LDAPATH", "SPK_EXEC", "SPK_EXEC_MEM", "TOP1M", "CUT", "MAXRESULTS", "ENSEMBLE", "EXPLAIN",
-            "HOLDOUT", "HOLDOUT_TOPICS", "TAIL")
+            "HOLDOUT", "HOLDOUT_TOPICS", "TAIL", "TAIL_TOL")
 
 # proxy has no multi-rank, sharded or HDFS-staged form
 PROXY_ONE_PROCESS = "proxy runs on one process: launch it without torchrun, with --gpus 1 and without --hdfs"
@@ -56,6 +56,11 @@ TAIL_ONE_PROCESS = "--tail runs on one process: launch it without torchrun, with
 # (256 / 1024 / 4096 measured on an MI355X: profiles/tail_mass.md)
 TAIL_BLOCK = 1024
 TAIL_SCRATCH_MB = 256      # cap on the per-block partials of one launch of ops.hip.tail_mass; more sides: batches
+# --tail-tol: pairs per distinct document from which score.scorer.tail_pairs takes ops.hip.tail_mass_docs (p once per
+# document of a tile) instead of ops.hip.tail_mass (p once per pair).  Both give the same bits: the value moves time
+# only.  Measured on an MI355X at 1 / 2 / 4 / 8 / 16 pairs per document (profiles/tail_rank.md section 2): at 1 the
+# shared-vector kernel loses (49 ms against 33 ms), from 2 on it wins (27 ms against 33 ms)
+TAIL_DOCS_MIN_SHARE = 2.0
 
 # --holdout: the split and the K fits are one process's: no multi-rank, sharded or HDFS-staged form
 HOLDOUT_ONE_PROCESS = "--holdout runs on one process: launch it without torchrun, with --gpus 1 and without --hdfs"
@@ -126,6 +131,9 @@ class RunConfig:
                                           # field of its word that makes it rare
     tail: bool = False                    # --tail / TAIL: also write <type>_tail.csv, per written side the host's
                                           # probability mass at or below the event's word
+    tail_tol: Optional[float] = None      # --tail-tol / TAIL_TOL: flag and rank the events by their tail p-value, the
+                                          # lower of the sides' tails, under this threshold (0 < P <= 1; implies
+                                          # tail); None: by the score under TOL, as ever
     holdout: float = 0.0                  # --holdout / HOLDOUT: hold this fraction of every document's tokens out, fit
                                           # on the rest and report the held-out perplexity per topic count; 0: off
     holdout_topics: str = ""              # --holdout-topics / HOLDOUT_TOPICS: "K1,K2,..." to evaluate; "": topics alone
@@ -204,6 +212,9 @@ class RunConfig:
             raise ValueError(HOST_REPORT_ONE_PROCESS)
         if self.explain and (self.gpus > 1 or self.hdfs):
             raise ValueError(EXPLAIN_ONE_PROCESS)
+        if self.tail_tol is not None:
+            self.tail_tol = self.check_tail_tol(self.tail_tol)
+            self.tail = True      # the tail file describes the rows the threshold chose
         if self.tail and (self.gpus > 1 or self.hdfs):
             raise ValueError(TAIL_ONE_PROCESS)
         self.check_ensemble(self.ensemble, self.start, self.gpus, self.hdfs)
@@ -214,6 +225,14 @@ class RunConfig:
     def holdout_list(self) -> List[int]:
         """The topic counts --holdout evaluates, in the order given: ``holdout_topics``, else ``topics`` alone."""
         return parse_topic_list(self.holdout_topics) or [int(self.topics)]
+
+    @staticmethod
+    def check_tail_tol(p) -> float:
+        """The --tail-tol rule, also applied by the command line before anything is written."""
+        p = float(p)
+        if not 0.0 < p <= 1.0:      # (a NaN fails both comparisons)
+            raise ValueError(f"--tail-tol must be in (0, 1], got {p}")
+        return p
 
     @staticmethod
     def check_holdout(holdout: float, topics: List[int], select: bool, start: str, compat: str, dsource: str,
@@ -319,6 +338,8 @@ def _apply(cfg: RunConfig, layer: Dict[str, object]):
         cfg.explain = str(layer["EXPLAIN"]).strip().lower() not in ("0", "false", "no", "off")
     if "TAIL" in layer and layer["TAIL"] not in ("", None):
         cfg.tail = str(layer["TAIL"]).strip().lower() not in ("0", "false", "no", "off")
+    if "TAIL_TOL" in layer and layer["TAIL_TOL"] not in ("", None):
+        cfg.tail_tol = float(layer["TAIL_TOL"])
     if "HOLDOUT" in layer and layer["HOLDOUT"] not in ("", None):
         cfg.holdout = float(layer["HOLDOUT"])
     if "HOLDOUT_TOPICS" in layer and layer["HOLDOUT_TOPICS"] not in ("", None):

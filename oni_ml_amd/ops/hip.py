@@ -629,32 +629,51 @@ def tail_mass(theta, phi, doc, word, block=None, max_blocks: int = 0, scratch_mb
     before the launch; ``n == 0`` launches nothing.  ``max_blocks``: cap on the workgroups per launch (tests: a
     small cap makes the grid-stride loops wrap).  ``block``: another block size (measurement:
     scripts/tail_bench.py)."""
+    return _tail_launch("tail_mass", False, theta, phi, doc, word, block, max_blocks, scratch_mb)
+
+
+def tail_mass_docs(theta, phi, doc, word, block=None, max_blocks: int = 0, scratch_mb=None):
+    """``tail_mass`` for pairs sorted by document (csrc/hip/tail_docs.hip): the same four tensors, bit for bit, with
+    p(.|d) evaluated once per (document of a tile of 256 pairs, phi row) and shared by the tile's pairs of that
+    document through LDS, instead of once per pair -- the shape of ranking every event of a day by its tail, where
+    the distinct pairs are the corpus entries and lie many to a document.
+
+    Arguments and refusals as ``tail_mass``, and: ``doc`` is non-decreasing, ``doc >= 0`` and ``word >= 0`` (the caller
+    drops sides without a row), else ``ValueError`` before any launch; repeated pairs are allowed.  Only the row
+    widths of the register ladder (``tail_theta_path(R, K) == "registers"``); any other is refused --
+    ``score.scorer.tail_pairs`` sends those to ``tail_mass``.  A scratch batch may end inside a document: a tile's
+    first pair starts a document slot of its own."""
+    return _tail_launch("tail_mass_docs", True, theta, phi, doc, word, block, max_blocks, scratch_mb)
+
+
+def _tail_launch(who, docs, theta, phi, doc, word, block, max_blocks, scratch_mb):
+    """The checks, the scratch batches and the launches of ``tail_mass`` and (``docs``) ``tail_mass_docs``."""
     import operator
     _max_blocks(max_blocks)
     TB = operator.index(_CFG.TAIL_BLOCK if block is None else block)
     if TB < 1:
-        raise ValueError(f"tail_mass: block must be >= 1, got {TB}")
+        raise ValueError(f"{who}: block must be >= 1, got {TB}")
     cap_mb = float(_CFG.TAIL_SCRATCH_MB if scratch_mb is None else scratch_mb)
     if not cap_mb > 0:
-        raise ValueError(f"tail_mass: scratch_mb must be > 0, got {scratch_mb!r}")
+        raise ValueError(f"{who}: scratch_mb must be > 0, got {scratch_mb!r}")
     if not isinstance(theta, torch.Tensor) or theta.dim() != 3:
         raise ValueError("theta: expected a [rows, R, K] tensor")
     R, K = int(theta.shape[1]), int(theta.shape[2])
     if not 1 <= R <= ENSEMBLE_MAX:
-        raise ValueError(f"tail_mass: R must be in [1, {ENSEMBLE_MAX}], got {R}")
+        raise ValueError(f"{who}: R must be in [1, {ENSEMBLE_MAX}], got {R}")
     if K < 1:
-        raise ValueError(f"tail_mass: K must be >= 1, got {K}")
+        raise ValueError(f"{who}: K must be >= 1, got {K}")
     _table3("theta", theta, R, K)
     dev = theta.device
     _table3("phi", phi, R, K, dev)
     V = int(phi.shape[0])
     if V >= 1 << 31 or TB >= 1 << 31:
-        raise ValueError(f"tail_mass: {V} phi rows, block {TB} (both < 2^31)")
+        raise ValueError(f"{who}: {V} phi rows, block {TB} (both < 2^31)")
     if not isinstance(doc, torch.Tensor) or doc.dim() != 1:
         raise ValueError("doc: expected a 1-D tensor")
     n = doc.numel()
     if n >= 1 << 31:
-        raise ValueError(f"tail_mass: {n} sides (n < 2^31)")
+        raise ValueError(f"{who}: {n} sides (n < 2^31)")
     _index("doc", doc, torch.int32, (n,), dev)
     _index("word", word, torch.int32, (n,), dev)
     le = torch.empty(n, dtype=torch.float64, device=dev)
@@ -665,11 +684,17 @@ def tail_mass(theta, phi, doc, word, block=None, max_blocks: int = 0, scratch_mb
         return le, tot, rarer, ties
     # index bounds (host check before a gather kernel touches memory)
     for name, idx, lim in (("doc", doc, theta.shape[0]), ("word", word, V)):
-        if int(idx.max()) >= lim or int(idx.min()) < -1:
+        if int(idx.max()) >= lim or int(idx.min()) < (0 if docs else -1):
             raise ValueError(f"{name}: index out of range")
+    if docs and n > 1 and bool((doc[1:] < doc[:-1]).any()):
+        raise ValueError(f"{who}: doc must be non-decreasing (the pairs sorted by document)")
     L = lib()
+    if docs and L.tail_theta_path(R, K) != 0:
+        raise ValueError(f"{who}: a row of {R} members x {K} topics is wider than the register ladder "
+                         f"(tail_theta_path: {tail_theta_path(R, K)}); tail_mass takes it")
+    launch = L.tail_mass_docs if docs else L.tail_mass
     if L.ensemble_max() != ENSEMBLE_MAX:
-        raise RuntimeError("tail_mass: config.ENSEMBLE_MAX differs from the compiled limit")
+        raise RuntimeError(f"{who}: config.ENSEMBLE_MAX differs from the compiled limit")
     nblk = -(-V // TB)
     per_side = 24 * max(nblk, 1)
     batch = max(1, min(n, int(cap_mb * (1 << 20)) // per_side))
@@ -678,10 +703,10 @@ def tail_mass(theta, phi, doc, word, block=None, max_blocks: int = 0, scratch_mb
     scratch = torch.empty(batch * max(nblk, 1) * 3, dtype=torch.float64, device=dev)
     for s0 in range(0, n, batch):
         m = min(batch, n - s0)
-        L.tail_mass(theta.data_ptr(), phi.data_ptr() if V else 0, R, K, V, doc.data_ptr() + 4 * s0,
-                    word.data_ptr() + 4 * s0, int(m), int(TB), int(nblk), scratch.data_ptr(), le.data_ptr() + 8 * s0,
-                    tot.data_ptr() + 8 * s0, rarer.data_ptr() + 4 * s0, ties.data_ptr() + 4 * s0, int(max_blocks),
-                    _stream())
+        launch(theta.data_ptr(), phi.data_ptr() if V else 0, R, K, V, doc.data_ptr() + 4 * s0,
+               word.data_ptr() + 4 * s0, int(m), int(TB), int(nblk), scratch.data_ptr(), le.data_ptr() + 8 * s0,
+               tot.data_ptr() + 8 * s0, rarer.data_ptr() + 4 * s0, ties.data_ptr() + 4 * s0, int(max_blocks),
+               _stream())
     return le, tot, rarer, ties
 
 

@@ -661,17 +661,85 @@ def write_explain(cfg, tables, order, key, sides, ex: ExplainInput, cols, sep: s
                 explain_max_group=dict(zip(names, (int(x) for x in largest))))
 
 
+@dataclass
+class TailRank:
+    """What ``tail_keys`` computed for every event of the day, on the scoring device: ``key`` the event's tail
+    p-value (NaN: no side has one) and ``flag`` (``key < cfg.tail_tol``), per side ``tail`` (NaN: none), ``tot``,
+    ``rarer`` (int64, -1: none) and ``pair`` (the side's distinct pair, -1: none), and the summary entries."""
+    key: torch.Tensor
+    flag: torch.Tensor
+    tail: tuple
+    tot: tuple
+    rarer: tuple
+    pair: tuple
+    stats: dict
+
+
+def tail_keys(cfg, model, side_docs, side_words, log=print) -> TailRank:
+    """--tail-tol: the tail p-value of every event (``side_docs`` / ``side_words``: the θ / φ row of every event's
+    side(s), -1: none).  Every side becomes the pair key ``d * V + w`` (-1 without a θ or a φ row); the distinct
+    keys, which ``SG.unique`` returns sorted by document, go through ``scorer.tail_pairs`` once, ``tail = le / tot``
+    is one rounded division, and the values are gathered back to the sides.  An event's key is the lowest of its
+    sides' tails, a NaN side ignored; with no side left the key is NaN and the event is never flagged.  ``flag`` is
+    ``key < cfg.tail_tol``.  From ``ops/sortgroup.py`` primitives and ``torch.where`` only (the cold-start rule of
+    docs/ARCHITECTURE.md)."""
+    from ..ops import sortgroup as SG
+    from ..score import scorer as S
+    theta, phi = S.model_tables3(model)
+    V, R, K = (int(x) for x in phi.shape)
+    dev = phi.device
+    n_sides = len(side_docs)
+    n = int(side_docs[0].numel())
+    doc = torch.cat([d.reshape(-1).to(torch.int64) for d in side_docs])
+    word = torch.cat([w.reshape(-1).to(torch.int64) for w in side_words])
+    ok = (doc >= 0) & (word >= 0)
+    nan = torch.full((n_sides * n,), float("nan"), dtype=torch.float64, device=dev)
+    tail, tot = nan, nan
+    rarer = torch.full((n_sides * n,), -1, dtype=torch.int64, device=dev)
+    pair = rarer
+    pairs, docs, skipped = 0, 0, 0
+    path = "cpu" if dev.type != "cuda" else "pairs"
+    if n:
+        pk, inv = SG.unique(torch.where(ok, doc * V + word, torch.full_like(doc, -1)), return_inverse=True)
+        none = int(pk[0] < 0)      # the -1 of the sides without a pair sorts first
+        pk = pk[none:]
+        pairs = int(pk.numel())
+        skipped = int((~ok).to(torch.int64).sum())
+        if pairs:
+            pd = pk // V
+            docs = SG.run_ids(pd)[1]
+            (le, tt, rr, _), path = S.tail_pairs(model, pd, pk - pd * V)
+            at = (inv - none).clamp_min(0)
+            tail = torch.where(ok, SG.gather(le / tt, at), nan)      # one rounded division
+            tot = torch.where(ok, SG.gather(tt, at), nan)
+            rarer = torch.where(ok, SG.gather(rr.to(torch.int64), at), rarer)
+            pair = torch.where(ok, at, pair)
+    side = lambda t: tuple(t[j * n:(j + 1) * n] for j in range(n_sides))      # noqa: E731
+    key = tail[:n]
+    for t in side(tail)[1:]:      # the lowest tail; a NaN side is ignored (NaN compares false)
+        key = torch.where((t == t) & ((key != key) | (t < key)), t, key)
+    flag = key < float(cfg.tail_tol)
+    log(f"{cfg.dsource}_post: tail of every event for --tail-tol {cfg.tail_tol}: {pairs} pairs of {docs} documents "
+        f"({path}), {docs} x {V} words x {K} topics x {R} members multiply-adds + {pairs} x {V} select-adds; "
+        f"{skipped} sides without a pair")
+    stats = dict(tail_tol=float(cfg.tail_tol), tail_rank_pairs=pairs, tail_rank_docs=docs, tail_rank_path=path,
+                 tail_sides_skipped=skipped)
+    return TailRank(key, flag, side(tail), side(tot), side(rarer), side(pair), stats)
+
+
 TAIL_DECADES = ("<1e-6", "<1e-5", "<1e-4", "<1e-3", "<1e-2", "<1e-1", "<=1")
 
 
-def write_tail(cfg, tables, order, key, sides, ex: ExplainInput, cols, sep: str = ",", log=print) -> dict:
+def write_tail(cfg, tables, order, key, sides, ex: ExplainInput, cols, sep: str = ",", log=print,
+               rank: Optional[TailRank] = None) -> dict:
     """--tail: ``<type>_tail.csv`` next to the results file, line i describing its line i (``order``: the written
     events; ``cols``: their ``row_cols``): the key score, then per side the document, the word, the side's score,
     ``tail`` and ``rarer``.  ``tail`` is the share of the document's probability mass -- over the scorer's whole φ
     table -- on the words whose score at this document is at most the side's (``scorer.tail_mass``: le / tot, one
     rounded division), ``rarer`` the number of words that score strictly lower; both empty for a side without a
     θ or a φ row.  The values depend on the pair (document, word) only: the distinct pairs of the written sides are
-    evaluated and gathered.  Returns the summary entries."""
+    evaluated (``scorer.tail_pairs``) and gathered.  ``rank`` (--tail-tol): every side's values are there already,
+    the written ones are gathered from them and nothing is launched.  Returns the summary entries."""
     from ..ops import native
     from ..ops import sortgroup as SG
     from ..score import scorer as S
@@ -684,7 +752,13 @@ def write_tail(cfg, tables, order, key, sides, ex: ExplainInput, cols, sep: str 
     tail = np.full(n_sides * n, np.nan)
     rarer = np.full(n_sides * n, -1, np.int64)
     pairs, tot_range = 0, None
-    if n:
+    if n and rank is not None:
+        take = lambda ts: torch.cat([SG.gather(t, o_t) for t in ts]).cpu().numpy()      # noqa: E731
+        tail, rarer, tot_w, pair_w = take(rank.tail), take(rank.rarer), take(rank.tot), take(rank.pair)
+        pairs = int(np.unique(pair_w[pair_w >= 0]).size)
+        if pairs:
+            tot_range = [float(tot_w[pair_w >= 0].min()), float(tot_w[pair_w >= 0].max())]
+    elif n:
         doc = torch.cat([SG.gather(sides[2 * j], o_t).to(torch.int64) for j in range(n_sides)])
         word = torch.cat([SG.gather(w, o_t).to(torch.int64) for w in ex.words])
         ok = (doc >= 0) & (word >= 0)
@@ -693,7 +767,7 @@ def write_tail(cfg, tables, order, key, sides, ex: ExplainInput, cols, sep: str 
         pk = pk[none:]
         pairs = int(pk.numel())
         if pairs:
-            le, tot, rr, _ = S.tail_mass(ex.model, pk // V, pk % V)
+            (le, tot, rr, _), _ = S.tail_pairs(ex.model, pk // V, pk % V)
             at = (inv - none).clamp_min(0)
             ok_h = ok.cpu().numpy()
             with np.errstate(invalid="ignore", divide="ignore"):
@@ -745,8 +819,9 @@ def one_sided_index(tables, ip_names, ip, unames, inv, device, ip_map=None):
 
 
 def rank_results(cfg, key, flag):
-    """(order, below, limit): the events under TOL ascending by ``key`` -- with MAXRESULTS only the ``limit``
-    lowest -- their count under TOL, and the limit (None: none)."""
+    """(order, below, limit): the flagged events ascending by ``key`` -- with MAXRESULTS only the ``limit``
+    lowest -- their count, and the limit (None: none).  ``key`` / ``flag``: the score key and its flag under TOL,
+    or under --tail-tol the tail key and flag of ``tail_keys``."""
     from ..score import scorer as S
     limit = cfg.max_results if cfg.max_results > 0 else None
     if limit is None:
@@ -757,13 +832,16 @@ def rank_results(cfg, key, flag):
 
 
 def write_results(cfg, tables, what: str, ranked, key, row_cols, events: int, sides, votes, log=print, ctx=None,
-                  sep: str = ",", extra=None, explain: Optional[ExplainInput] = None) -> dict:
+                  sep: str = ",", extra=None, explain: Optional[ExplainInput] = None,
+                  tail_rank: Optional[TailRank] = None) -> dict:
     """``<type>_results.csv`` from ``ranked`` (what ``rank_results`` returned) and the scorer's ``row_cols``, the
     log line, and the scoring stage's result.  One process: the rows, then the host report (``sides``: the
     ``doc_a, score_a, doc_b, score_b`` of ``write_host_report``) and the votes histogram.  Several ranks
     (``ctx``): the ranks' rows merged into one ascending file (``shardio.merge_sorted_rows``, the sortByKey
     shuffle), the counts summed.  ``extra``: further result entries.  ``explain``: the sides' φ rows and columns
-    for ``write_explain`` and ``write_tail`` (one process, under --explain / --tail)."""
+    for ``write_explain`` and ``write_tail`` (one process, under --explain / --tail).  ``tail_rank`` (--tail-tol):
+    what ``tail_keys`` returned -- ``ranked`` was made from its key and flag, ``key`` stays the score key that the
+    files' columns hold."""
     from ..ops import native
     order, below, limit = ranked
     n = int(order.size)
@@ -780,12 +858,19 @@ def write_results(cfg, tables, what: str, ranked, key, row_cols, events: int, si
             f"({n} from rank {ctx.rank})")
         return dict(flagged=total, below_tol=below, rank_flagged=n, events=ctx.allreduce_int(events), **(extra or {}))
     native.lib().write_rows(out, None, cols, sep=sep, threads=cfg.threads, n=n)
-    log(f"{cfg.dsource}_post: {flagged_text(n, below, limit, what, cfg.tol)} written to {out}")
+    if tail_rank is not None:
+        of = "" if limit is None else f" of the {below}"
+        log(f"{cfg.dsource}_post: {n}{of} {what} with tail < {cfg.tail_tol}"
+            f"{'' if limit is None else f' (MAXRESULTS {limit})'} written to {out}")
+    else:
+        log(f"{cfg.dsource}_post: {flagged_text(n, below, limit, what, cfg.tol)} written to {out}")
     hosts = write_host_report(cfg, tables, *sides, row_cols, sep=sep, log=log) if cfg.host_report else {}
     why = write_explain(cfg, tables, order, key, sides, explain, cols, sep=sep, log=log) if cfg.explain else {}
-    tail = write_tail(cfg, tables, order, key, sides, explain, cols, sep=sep, log=log) if cfg.tail else {}
+    tail = write_tail(cfg, tables, order, key, sides, explain, cols, sep=sep, log=log,
+                      rank=tail_rank) if cfg.tail else {}
     return dict(flagged=n, below_tol=below, events=events, **(extra or {}), **hosts,
-                **votes_hist(votes, order, cfg.ensemble), **why, **tail)
+                **votes_hist(votes, order, cfg.ensemble), **why, **tail,
+                **(tail_rank.stats if tail_rank is not None else {}))
 
 
 def save_json(path: str, obj):

@@ -88,7 +88,9 @@ def score_dns(cfg, tab: FD.DnsTable, top, tables: C.ModelTables, device, log=pri
         raise ValueError("compat=strict scores over exactly 20 topics (dns_post_lda.scala:316)")
     model = S.build_model(tables, th, ph, S.default_value("dns", K, cfg.strict), device)
     sc, _, key, flag, votes = S.score_votes(model, didx, widx, None, None, cfg.tol)
-    ranked = C.rank_results(cfg, key, flag)
+    # --tail-tol: the events are flagged and ranked by their tail p-value; the files' score columns stay
+    tr = C.tail_keys(cfg, model, (didx,), (widx,), log=log) if cfg.tail_tol is not None else None
+    ranked = C.rank_results(cfg, key, flag) if tr is None else C.rank_results(cfg, tr.key, tr.flag)
     H = feat.host
 
     def row_cols(order):
@@ -110,7 +112,8 @@ def score_dns(cfg, tab: FD.DnsTable, top, tables: C.ModelTables, device, log=pri
         ]
     return C.write_results(cfg, tables, "queries", ranked, key, row_cols, int(feat.word_key.numel()),
                            (didx, sc, None, None), votes, log, ctx=ctx,
-                           explain=C.ExplainInput(model, (widx,), ((feat.ip_names, feat.ip),), ((-2, -1),)))
+                           explain=C.ExplainInput(model, (widx,), ((feat.ip_names, feat.ip),), ((-2, -1),)),
+                           tail_rank=tr)
 
 
 def synthetic_dns_corpus(events: int = 2_000_000, seed: int = 0, device=None, strict: bool = True, threads: int = 8,

@@ -166,6 +166,9 @@ def run_stages(cfg, spec: PipelineSpec, device=None, log=print) -> dict:
                     R.emit(dict(stage=post_stage + "_detail", **why))
                 if cfg.tail:
                     tail = {k: res[k] for k in ("tail_words", "tail_pairs", "tail_hist", "tail_total_range")}
+                    if cfg.tail_tol is not None:      # flagged and ranked by the tail: what that took
+                        tail.update({k: res[k] for k in ("tail_tol", "tail_rank_pairs", "tail_rank_docs",
+                                                         "tail_rank_path", "tail_sides_skipped")})
                     summary.update(tail)
                     R.emit(dict(stage=post_stage + "_detail", **tail))
         else:

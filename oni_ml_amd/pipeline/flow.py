@@ -137,7 +137,9 @@ def score_flow(cfg, ft: FF.FlowTable, tables: C.ModelTables, device, log=print, 
     d_src, d_dst = SG.gather(didx, feat.sip), SG.gather(didx, feat.dip)
     sa, sb, key, flag, votes = S.score_votes(model, d_src, w_src, d_dst, w_dst, cfg.tol)
     qs = S.key_quantiles(key)
-    ranked = C.rank_results(cfg, key, flag)
+    # --tail-tol: the events are flagged and ranked by their tail p-value; the files' score columns stay
+    tr = C.tail_keys(cfg, model, (d_src, d_dst), (w_src, w_dst), log=log) if cfg.tail_tol is not None else None
+    ranked = C.rank_results(cfg, key, flag) if tr is None else C.rank_results(cfg, tr.key, tr.flag)
     # output columns: 27 raw + time + ibyt_bin + ipkt_bin + time_bin + word_port + ip_pair + src/dest word + scores
     def row_cols(order):
         """The 37 columns of the given events, in that order."""
@@ -167,7 +169,8 @@ def score_flow(cfg, ft: FF.FlowTable, tables: C.ModelTables, device, log=print, 
     return C.write_results(cfg, tables, "events", ranked, key, row_cols, int(feat.time.numel()),
                            (d_src, sa, d_dst, sb), votes, log, ctx=ctx, extra=qs,
                            explain=C.ExplainInput(model, (w_src, w_dst), ((ipn, feat.sip), (ipn, feat.dip)),
-                                                  ((-4, -2), (-3, -1))))
+                                                  ((-4, -2), (-3, -1))),
+                           tail_rank=tr)
 
 
 def synthetic_flow_corpus(events: int = 1_000_000, seed: int = 0, workdir: Optional[str] = None, device=None,

@@ -259,6 +259,31 @@ def tail_mass(model, doc: torch.Tensor, word: torch.Tensor):
     return fn(theta.contiguous(), phi.contiguous(), i32(doc), i32(word))
 
 
+def tail_pairs(model, doc: torch.Tensor, word: torch.Tensor):
+    """``((le, tot, rarer, ties), path)`` of (document, word) pairs sorted by document, every ``doc >= 0`` and
+    ``word >= 0`` -- what ``SG.unique`` of the keys ``d * V + w`` gives.  The values are ``tail_mass``'s bit for bit
+    whichever path computes them, so the choice shows in no file:
+      ``"docs"``   ``ops.hip.tail_mass_docs`` -- on the GPU, where the register ladder holds the row width and the
+                   pairs per distinct document are at least ``config.TAIL_DOCS_MIN_SHARE``;
+      ``"pairs"``  ``ops.hip.tail_mass`` -- on the GPU otherwise;
+      ``"cpu"``    ``ops.reference.tail_mass`` -- on the CPU, always."""
+    from ..config import TAIL_DOCS_MIN_SHARE
+    from ..ops import sortgroup as SG
+    theta, phi = model_tables3(model)
+    theta, phi = theta.contiguous(), phi.contiguous()
+    d32, w32 = doc.to(torch.int32).contiguous(), word.to(torch.int32).contiguous()
+    if theta.device.type != "cuda":
+        from ..ops.reference import tail_mass as ref
+        return ref(theta, phi, d32, w32), "cpu"
+    from ..ops import hip as H
+    n = int(d32.numel())
+    if n and H.tail_theta_path(int(theta.shape[1]), int(theta.shape[2])) == "registers":
+        docs = SG.run_ids(d32.to(torch.int64))[1]
+        if n >= TAIL_DOCS_MIN_SHARE * docs:
+            return H.tail_mass_docs(theta, phi, d32, w32), "docs"
+    return H.tail_mass(theta, phi, d32, w32), "pairs"
+
+
 def rank_hosts(min_score: torch.Tensor, flagged: torch.Tensor, limit: Optional[int] = None) -> np.ndarray:
     """Document rows with at least one flagged side, ascending by their lowest score, ties to the lowest row
     (int64 host array); ``limit``: only the first ``limit`` of them (the MAXRESULTS radix select and its tie
