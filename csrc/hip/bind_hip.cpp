@@ -213,6 +213,19 @@ PYBIND11_MODULE(_onihip, m) {
     oni::launch_explain_sides(a, max_blocks, S(stream));
   });
 
+  m.def("expect_theta_path", [](int R, int K) { return oni::expect_theta_path(R, K); });
+  m.def("expect_sides", [](u theta, u phi, int R, int K, double dflt, u order, u doc, u word, u seg_start, u seg_end,
+                           u out_at, u blk_off, u blk_item, int64_t n, int64_t B, int block, u part_p, u part_best,
+                           u part_above, u best, u pbest, u above, int max_blocks, u stream) {
+    oni::ExpectArgs a{P<const double>(theta),      P<const double>(phi),      R, K, dflt,
+                      P<const int>(order),         P<const int>(doc),         P<const int>(word),
+                      P<const int64_t>(seg_start), P<const int64_t>(seg_end), P<const int64_t>(out_at),
+                      P<const int64_t>(blk_off),   P<const int>(blk_item),    n, B, block,
+                      P<double>(part_p),           P<int>(part_best),         P<int>(part_above),
+                      P<int>(best),                P<double>(pbest),          P<int>(above)};
+    oni::launch_expect_sides(a, max_blocks, S(stream));
+  });
+
   m.def("tail_theta_path", [](int R, int K) { return oni::tail_theta_path(R, K); });
   m.def("tail_mass", [](u theta, u phi, int R, int K, int64_t V, u doc, u word, int64_t n, int64_t block,
                         int64_t nblk, u scratch, u le, u tot, u rarer, u ties, int max_blocks, u stream) {

@@ -328,6 +328,43 @@ struct ExplainArgs {
 // max_blocks: cap on the workgroups (0: 8192)
 void launch_explain_sides(const ExplainArgs& a, int max_blocks, hipStream_t s);
 
+// --expect (expect.hip).  An item is a (document, word) pair and one explained field of the word: its group is the
+// segment order[seg_start, seg_end) of phi rows.  p_v = the pair's score with member row v in place of its word, as
+// score_ensemble computes it (doc < 0: the default vector for theta); s = p_word.  best = the member with the
+// greatest p_v under IEEE > (a NaN never wins, ties to the lowest row, -0.0 and +0.0 tie), pbest its p_v, above =
+// #{p_v > s}.  An item with seg_start < 0 (no word or no group) gets -1, NaN, -1; an empty segment -1, NaN, 0.
+// Max, lowest-row tie-break and an integer count: the same bits for every grid and every block cut, no atomics.
+struct ExpectArgs {
+  const double* theta;       // [D][R][K]
+  const double* phi;         // [V][R][K]
+  int R, K;                  // 1 <= R <= kEnsembleMax, K >= 1
+  double dflt;               // value of the default vector of an item without a document
+  const int* order;          // [n_ord] phi rows, every value in [0, V) (checked on the host)
+  const int* doc;            // [n] theta row or -1
+  const int* word;           // [n] phi row, in [0, V) where seg_start >= 0
+  const int64_t* seg_start;  // [n] -1: no value; else 0 <= seg_start <= seg_end <= n_ord (checked on the host)
+  const int64_t* seg_end;    // [n]
+  const int64_t* out_at;     // [n] where the item's results go in best / pbest / above
+  const int64_t* blk_off;    // [n + 1] exclusive prefix sum of the items' block counts ceil(len / block)
+  const int* blk_item;       // [B] the item of every block
+  int64_t n;                 // items, 0 <= n < 2^31
+  int64_t B;                 // blocks of all items, blk_off[n], < 2^31
+  int block;                 // members of a block, >= 1
+  double* part_p;            // [B] per-block pbest of the items of more than one block
+  int* part_best;            // [B] per-block best
+  int* part_above;           // [B] per-block above
+  int* best;                 // [n]
+  double* pbest;             // [n]
+  int* above;                // [n]
+};
+enum ExpectPath : int {
+  kExpectRegisters = 0,   // theta row in registers (the ladder of tail_common.h)
+  kExpectGlobal = 1,      // theta row read from global memory at every member
+};
+int expect_theta_path(int R, int K);
+// max_blocks: cap on the workgroups per launch (0: 65536)
+void launch_expect_sides(const ExpectArgs& a, int max_blocks, hipStream_t s);
+
 // --tail (tail_mass.hip).  For side i with doc[i] >= 0 and word[i] >= 0, over every row v of phi: p_v = the
 // side's score with row v in place of its word, as score_ensemble computes it; s = p_word.  The rows are cut into
 // nblk blocks of `block`; within a block, from 0.0 in row order, le_b += (p_v <= s ? p_v : 0.0) and tot_b += p_v;

@@ -1,7 +1,8 @@
 // What the tail kernels share (tail_mass.hip: a side at a time; tail_docs.hip: a document's pairs share p): the
 // partial sums of a side and a vocabulary block, the select-add, the scorers' member dots over plain and over padded
 // rows, the staging of padded phi rows in LDS, the scratch cell of a (block, side) and the register ladder.  One
-// definition, so the two kernels cannot drift apart in a bit.
+// definition, so the two kernels cannot drift apart in a bit.  expect.hip takes its member dots (dot_any, dot_reg)
+// and the ladder from here too.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -64,6 +65,47 @@ __device__ __forceinline__ double dot_pad(const double (&th)[TK * TM], const dou
         acc = acc + p0;
         const double p1 = th[m * TK + k + 1] * q.y;
         acc = acc + p1;
+      }
+      sum = sum + acc;
+    }
+  }
+  return R == 1 ? sum : sum / rd;
+}
+
+// the same with th padded in registers [TM][TK] and p one plain row [R][K] in global memory (expect.hip: the rows
+// of a group are gathered through an order, so nothing stages them).  A member's loads are issued together, ahead
+// of the sums: a topic past K loads the row's last topic again and is left out of the sum (it would add 0.0 * x to
+// a sum that started at +0.0).  VEC: K even and p 16-byte aligned, two topics per load.
+template <int TK, int TM, bool VEC>
+__device__ __forceinline__ double dot_reg(const double (&th)[TK * TM], const double* __restrict__ p, int R, int K,
+                                          double rd) {
+#pragma clang fp contract(off)
+  double sum = 0.0;
+#pragma unroll
+  for (int m = 0; m < TM; ++m) {
+    if (m < R) {   // uniform
+      const double* pm = p + m * K;
+      double2 q[TK / 2];
+#pragma unroll
+      for (int k = 0; k < TK; k += 2) {
+        if (VEC) {
+          q[k / 2] = reinterpret_cast<const double2*>(pm)[(k < K ? k : K - 2) / 2];
+        } else {
+          q[k / 2].x = pm[k < K ? k : K - 1];
+          q[k / 2].y = pm[k + 1 < K ? k + 1 : K - 1];
+        }
+      }
+      double acc = 0.0;
+#pragma unroll
+      for (int k = 0; k < TK; k += 2) {
+        if (k < K) {   // uniform
+          const double p0 = th[m * TK + k] * q[k / 2].x;
+          acc = acc + p0;
+        }
+        if (k + 1 < K) {
+          const double p1 = th[m * TK + k + 1] * q[k / 2].y;
+          acc = acc + p1;
+        }
       }
       sum = sum + acc;
     }

@@ -92,12 +92,13 @@ def _apply_lda_args(a, st):
 
 def clean_workdir(lpath: str):
     """ml_ops.sh:53-54: remove stale *.dat,*.beta,*.gamma,*.other,*.pkl; keep *.csv (analyst feedback) -- except
-    what an earlier --explain or --tail run left, ``<type>_explain.csv``, ``word_fields.npz`` and
-    ``<type>_tail.csv``: a fresh run removes them with or without the flags, since their lines would not describe
-    this run's results file.  ``ensemble/`` and ``holdout/`` (an earlier run's members, its held-out records and
-    training fits) go too."""
+    what an earlier --explain, --expect or --tail run left, ``<type>_explain.csv``, ``word_fields.npz``,
+    ``<type>_expect.csv`` and ``<type>_tail.csv``: a fresh run removes them with or without the flags, since their
+    lines would not describe this run's results file.  ``ensemble/`` and ``holdout/`` (an earlier run's members, its
+    held-out records and training fits) go too."""
     for pat in ("*.dat", "*.beta", "*.gamma", "*.other", "*.pkl", "checkpoint.npz", "final_model.npz",
-                "final_gamma.rank*.npz", "word_fields.npz", "*_explain.csv", "*_tail.csv"):
+                "final_gamma.rank*.npz", "word_fields.npz", "*_explain.csv", "*_expect.csv",
+                "*_tail.csv"):
         for f in glob.glob(os.path.join(lpath, pat)):
             os.unlink(f)
     shutil.rmtree(os.path.join(lpath, ".stages"), ignore_errors=True)
@@ -122,6 +123,10 @@ def cmd_ml_ops(argv):
     ap.add_argument("--explain", action="store_true", default=None,
                     help="also write <type>_explain.csv: per written side the field of its word that makes it rare "
                          "and the conditional probability of every field (or EXPLAIN=1; one process only)")
+    ap.add_argument("--expect", action="store_true", default=None,
+                    help="also write <type>_expect.csv: per written side and explained field the value its host would "
+                         "normally show there, how many times more probable that value is than the event's, and how "
+                         "many values beat the event's.  Implies --explain (or EXPECT=1; one process only)")
     ap.add_argument("--tail", action="store_true", default=None,
                     help="also write <type>_tail.csv: per written side the share of its host's probability mass on "
                          "words as rare as the event's or rarer, a p-value comparable across hosts (or TAIL=1; one "
@@ -190,8 +195,8 @@ def cmd_ml_ops(argv):
                            write_doc_wc=a.keep_doc_wc, word_assignments=a.word_assignments,
                            rank_gamma=a.rank_gamma, verbose=not a.quiet, cuts=a.cuts, hdfs=a.hdfs or None,
                            hadoop=a.hadoop, host_report=a.host_report, ensemble=a.ensemble, explain=a.explain,
-                           tail=a.tail, tail_tol=a.tail_tol, holdout=a.holdout, holdout_topics=a.holdout_topics,
-                           holdout_select=a.holdout_select)
+                           expect=a.expect, tail=a.tail, tail_tol=a.tail_tol, holdout=a.holdout,
+                           holdout_topics=a.holdout_topics, holdout_select=a.holdout_select)
     # --ensemble / ENSEMBLE (the site file and the environment set it too): refused here, before anything is
     # written and before a process group is asked for
     first = resolve(1)
@@ -199,6 +204,9 @@ def cmd_ml_ops(argv):
     # --explain / EXPLAIN likewise
     if first.explain and (a.gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1 or a.hdfs):
         raise ValueError(CFG.EXPLAIN_ONE_PROCESS)
+    # --expect / EXPECT likewise
+    if first.expect and (a.gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1 or a.hdfs):
+        raise ValueError(CFG.EXPECT_ONE_PROCESS)
     # --tail / TAIL and --tail-tol / TAIL_TOL likewise
     if first.tail_tol is not None:
         CFG.RunConfig.check_tail_tol(first.tail_tol)

@@ -27,7 +27,7 @@ from .models.lda.settings import LDASettings
 
 ENV_KEYS = ("FLOW_PATH", "DNS_PATH", "PROXY_PATH", "HPATH", "LPATH", "LUSER", "TOL", "DUPFACTOR", "KRB_AUTH", "NODES",
             "UINODE", "RPATH", "LDAPATH", "SPK_EXEC", "SPK_EXEC_MEM", "TOP1M", "CUT", "MAXRESULTS", "ENSEMBLE", "EXPLAIN",
-            "HOLDOUT", "HOLDOUT_TOPICS", "TAIL", "TAIL_TOL")
+            "HOLDOUT", "HOLDOUT_TOPICS", "TAIL", "TAIL_TOL", "EXPECT")
 
 # proxy has no multi-rank, sharded or HDFS-staged form
 PROXY_ONE_PROCESS = "proxy runs on one process: launch it without torchrun, with --gpus 1 and without --hdfs"
@@ -47,6 +47,9 @@ EXPLAIN_MAX_FIELDS = 8     # explained fields of a word space (csrc/hip/kernels.
 # block in member order, then the block sums in block order; the value is part of the result's bits
 GROUP_BLOCK = 256
 WORD_FIELDS = "word_fields.npz"      # <LPATH>/word_fields.npz: the vocabulary's keys and fields, under --explain
+
+# the expect file is made from the explain file's groups and sides: the same one-process rule
+EXPECT_ONE_PROCESS = "--expect runs on one process: launch it without torchrun, with --gpus 1 and without --hdfs"
 
 # the tail file is made from one process's scored sides and its model tables: no multi-rank, sharded or HDFS-staged
 # form
@@ -129,6 +132,9 @@ class RunConfig:
                                           # side under TOL, N >= 1: the N hosts with the lowest scores
     explain: bool = False                 # --explain / EXPLAIN: also write <type>_explain.csv, per written side the
                                           # field of its word that makes it rare
+    expect: bool = False                  # --expect / EXPECT: also write <type>_expect.csv, per written side and
+                                          # explained field the value the host would normally show there (implies
+                                          # explain)
     tail: bool = False                    # --tail / TAIL: also write <type>_tail.csv, per written side the host's
                                           # probability mass at or below the event's word
     tail_tol: Optional[float] = None      # --tail-tol / TAIL_TOL: flag and rank the events by their tail p-value, the
@@ -210,6 +216,10 @@ class RunConfig:
             raise ValueError(f"--host-report must be 0 (off), -1 (every flagged host) or >= 1, got {self.host_report}")
         if self.host_report and (self.gpus > 1 or self.hdfs):
             raise ValueError(HOST_REPORT_ONE_PROCESS)
+        if self.expect:
+            if self.gpus > 1 or self.hdfs:
+                raise ValueError(EXPECT_ONE_PROCESS)
+            self.explain = True      # the expect file describes the explain file's sides through its groups
         if self.explain and (self.gpus > 1 or self.hdfs):
             raise ValueError(EXPLAIN_ONE_PROCESS)
         if self.tail_tol is not None:
@@ -336,6 +346,8 @@ def _apply(cfg: RunConfig, layer: Dict[str, object]):
         cfg.ensemble = int(layer["ENSEMBLE"])
     if "EXPLAIN" in layer and layer["EXPLAIN"] not in ("", None):
         cfg.explain = str(layer["EXPLAIN"]).strip().lower() not in ("0", "false", "no", "off")
+    if "EXPECT" in layer and layer["EXPECT"] not in ("", None):
+        cfg.expect = str(layer["EXPECT"]).strip().lower() not in ("0", "false", "no", "off")
     if "TAIL" in layer and layer["TAIL"] not in ("", None):
         cfg.tail = str(layer["TAIL"]).strip().lower() not in ("0", "false", "no", "off")
     if "TAIL_TOL" in layer and layer["TAIL_TOL"] not in ("", None):

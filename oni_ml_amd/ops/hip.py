@@ -603,6 +603,131 @@ def explain_sides(theta, phi, gsum, doc, word, grow, dflt, max_blocks: int = 0):
     return cond, why
 
 
+EXPECT_FORMS = ("blocks",)      # the forms of the expect kernel that ship (profiles/expect.md)
+EXPECT_PATHS = ("registers", "global")
+
+
+def expect_theta_path(R: int, K: int) -> str:
+    """Where the expect kernel keeps a theta row of R members x K topics (csrc/hip/expect.hip): in ``registers`` on
+    the ladder of tail_common.h, or read from ``global`` memory at every member."""
+    return EXPECT_PATHS[lib().expect_theta_path(int(R), int(K))]
+
+
+def expect_sides(theta, phi, order, seg_start, seg_end, doc, word, grow, dflt, max_blocks: int = 0, block=None,
+                 form=None):
+    """Per (document, word) pair and explained field the member of the word's group that the document's model
+    finds most probable (csrc/hip/expect.hip; ``ops.reference.expect_sides`` is the twin):
+    ``(best int32 [n, F], pbest float64 [n, F], above int32 [n, F])`` as new device tensors.
+
+    ``theta`` [D, R, K] / ``phi`` [V, R, K] as ``score_ensemble`` takes them; ``order`` int32 [n_ord] of phi rows,
+    ``seg_start`` / ``seg_end`` int64 [G] with 0 <= start <= end <= n_ord: group g is ``order[start[g] : end[g]]``;
+    ``doc`` / ``word`` int32 [n] rows or -1, ``grow`` int32 [n, F] the group of the pair's field f or -1.  p_v is
+    the pair's ``score_ensemble`` score with phi row v in place of the word (a pair without a document takes the
+    default vector), s = p_word.  ``best``: the member with the greatest p_v under ``>`` -- a NaN never wins, ties
+    to the lowest row -- or -1; ``pbest`` its p_v (NaN without one); ``above`` the members with p_v > s.  ``word
+    < 0`` or ``grow < 0``: -1, NaN, -1.  A maximum, a tie-break by row and a count: the same bits for every grid
+    and block cut, no atomics.
+
+    The items (pair, field) are sorted by group before the launch (``ops/sortgroup.py``), a group is cut into
+    blocks of ``config.GROUP_BLOCK`` members, a lane per (item, block).  Everything is checked on the host before
+    the launch (host reads: the bounds of every index, the block count); ``n == 0`` launches nothing.
+    ``max_blocks``: cap on the workgroups per launch (tests: a small cap makes the grid-stride loops wrap).
+    ``block``: another block size (measurement: scripts/expect_bench.py).  ``form``: one of ``EXPECT_FORMS`` (None:
+    the default)."""
+    import operator
+
+    from . import sortgroup as SG
+    _max_blocks(max_blocks)
+    if form is not None and form not in EXPECT_FORMS:
+        raise ValueError(f"expect_sides: form must be one of {EXPECT_FORMS}, got {form!r}")
+    GB = operator.index(_CFG.GROUP_BLOCK if block is None else block)
+    if not 1 <= GB < 1 << 31:
+        raise ValueError(f"expect_sides: block must be in [1, 2^31), got {GB}")
+    if not isinstance(theta, torch.Tensor) or theta.dim() != 3:
+        raise ValueError("theta: expected a [rows, R, K] tensor")
+    R, K = int(theta.shape[1]), int(theta.shape[2])
+    if not 1 <= R <= ENSEMBLE_MAX:
+        raise ValueError(f"expect_sides: R must be in [1, {ENSEMBLE_MAX}], got {R}")
+    if K < 1:
+        raise ValueError(f"expect_sides: K must be >= 1, got {K}")
+    _table3("theta", theta, R, K)
+    dev = theta.device
+    _table3("phi", phi, R, K, dev)
+    V = int(phi.shape[0])
+    if V >= 1 << 31:
+        raise ValueError(f"expect_sides: {V} phi rows (V < 2^31)")
+    if not isinstance(order, torch.Tensor) or order.dim() != 1:
+        raise ValueError("order: expected a 1-D tensor")
+    n_ord = order.numel()
+    p_ord = _index("order", order, torch.int32, (n_ord,), dev)
+    if not isinstance(seg_start, torch.Tensor) or seg_start.dim() != 1:
+        raise ValueError("seg_start: expected a 1-D tensor")
+    G = seg_start.numel()
+    _index("seg_start", seg_start, torch.int64, (G,), dev)
+    _index("seg_end", seg_end, torch.int64, (G,), dev)
+    if not isinstance(doc, torch.Tensor) or doc.dim() != 1:
+        raise ValueError("doc: expected a 1-D tensor")
+    n = doc.numel()
+    if not isinstance(grow, torch.Tensor) or grow.dim() != 2:
+        raise ValueError("grow: expected an [n, F] tensor")
+    F = int(grow.shape[1])
+    if not 1 <= F <= _CFG.EXPLAIN_MAX_FIELDS:
+        raise ValueError(f"expect_sides: F must be in [1, {_CFG.EXPLAIN_MAX_FIELDS}], got {F}")
+    M = n * F
+    if M >= 1 << 31:
+        raise ValueError(f"expect_sides: {n} pairs x {F} fields (n F < 2^31)")
+    _index("doc", doc, torch.int32, (n,), dev)
+    _index("word", word, torch.int32, (n,), dev)
+    _index("grow", grow, torch.int32, (n, F), dev)
+    best = torch.empty((n, F), dtype=torch.int32, device=dev)
+    pbest = torch.empty((n, F), dtype=torch.float64, device=dev)
+    above = torch.empty((n, F), dtype=torch.int32, device=dev)
+    if n == 0:
+        return best, pbest, above
+    # bounds (host checks before a gather kernel touches memory)
+    for name, idx, lim in (("doc", doc, theta.shape[0]), ("word", word, V), ("grow", grow, G)):
+        if int(idx.max()) >= lim or int(idx.min()) < -1:
+            raise ValueError(f"{name}: index out of range")
+    if n_ord and (int(order.min()) < 0 or int(order.max()) >= V):
+        raise ValueError("order: index out of range")
+    if G and (int(seg_start.min()) < 0 or int((seg_end - seg_start).min()) < 0 or int(seg_end.max()) > n_ord):
+        raise ValueError(f"seg_start / seg_end: segments must satisfy 0 <= start <= end <= {n_ord}")
+    L = lib()
+    if L.ensemble_max() != ENSEMBLE_MAX or L.explain_max_fields() != _CFG.EXPLAIN_MAX_FIELDS:
+        raise RuntimeError("expect_sides: config.ENSEMBLE_MAX / EXPLAIN_MAX_FIELDS differ from the compiled limits")
+    # the items (pair, field), sorted by group: the lanes of a wave then walk the same member rows
+    g = grow.reshape(-1).to(torch.int64)
+    pair = torch.arange(M, device=dev, dtype=torch.int64) // F
+    valid = (g >= 0) & (SG.gather(word, pair) >= 0)
+    _, perm = SG.sort_stable(torch.where(valid, g, torch.full_like(g, G)))
+    it_pair = SG.gather(pair, perm)
+    ok = SG.gather(valid, perm)
+    none = torch.full((M,), -1, dtype=torch.int64, device=dev)
+    if G:
+        gs = SG.gather(g, perm).clamp_min(0)
+        it_start = torch.where(ok, SG.gather(seg_start, gs), none)
+        it_end = torch.where(ok, SG.gather(seg_end, gs), none)
+    else:      # no group at all: every grow is -1 (checked above)
+        it_start = it_end = none
+    it_doc = SG.gather(doc, it_pair).contiguous()
+    it_word = SG.gather(word, it_pair).contiguous()
+    nb = (it_end - it_start + (GB - 1)) // GB      # 0 without a value (-1 - -1) and for an empty group
+    blk_off = torch.zeros(M + 1, dtype=torch.int64, device=dev)
+    blk_off[1:] = torch.cumsum(nb, 0)
+    B = int(blk_off[-1])
+    if B >= 1 << 31:
+        raise ValueError(f"expect_sides: {B} blocks (B < 2^31)")
+    blk_item = SG.segment_ids(nb, B).to(torch.int32)
+    part_p = torch.empty(max(B, 1), dtype=torch.float64, device=dev)
+    part_i = torch.empty((2, max(B, 1)), dtype=torch.int32, device=dev)
+    L.expect_sides(theta.data_ptr(), phi.data_ptr() if V else 0, R, K, float(dflt), p_ord, it_doc.data_ptr(),
+                   it_word.data_ptr(), it_start.data_ptr(), it_end.data_ptr(), perm.data_ptr(), blk_off.data_ptr(),
+                   blk_item.data_ptr(), int(M), int(B), int(GB), part_p.data_ptr(), part_i[0].data_ptr(),
+                   part_i[1].data_ptr(), best.data_ptr(), pbest.data_ptr(), above.data_ptr(), int(max_blocks),
+                   _stream())
+    return best, pbest, above
+
+
 TAIL_PATHS = ("registers", "lds_theta", "direct")
 
 

@@ -235,6 +235,91 @@ def explain_sides(theta, phi, gsum, doc, word, grow, dflt):
     return cond, why
 
 
+EXPECT_SLAB = 1 << 20      # (item, member) dots the expect twin holds at a time
+
+
+def expect_sides(theta, phi, order, seg_start, seg_end, doc, word, grow, dflt, slab: int = EXPECT_SLAB):
+    """Torch twin of ``ops.hip.expect_sides`` (csrc/hip/expect.hip) on any device, bit for bit, and the CPU
+    pipeline's path: ``(best int32 [n, F], pbest float64 [n, F], above int32 [n, F])``.  ``theta`` [D, R, K],
+    ``phi`` [V, R, K]; group g is the phi rows ``order[seg_start[g] : seg_end[g]]``; ``doc`` / ``word`` [n] rows or
+    -1, ``grow`` [n, F] groups or -1.  For an item (pair i, field f) with a word and a group, p_v is the pair's
+    ``score_ensemble`` score with member row v in place of the word -- taken from the ``score_ensemble`` twin itself,
+    so s = p_word and every p_v are the scorer's bits -- ``best`` the member with the greatest p_v under ``>`` (a
+    NaN never wins, ties to the lowest row, -0.0 and +0.0 tie; -1 without one), ``pbest`` its p_v (NaN without
+    one), ``above`` the members with ``p_v > s``.  An item without a word or a group gets -1, NaN, -1.  Items are
+    taken in slabs of at most ``slab`` member dots (a single longer group is a slab of its own)."""
+    import bisect
+
+    from . import sortgroup as SG
+    if theta.dim() != 3 or phi.dim() != 3 or theta.shape[1:] != phi.shape[1:] or theta.dtype != torch.float64 \
+            or phi.dtype != torch.float64:
+        raise ValueError("expect_sides: theta [D, R, K] and phi [V, R, K] float64")
+    if grow.dim() != 2 or grow.shape[0] != doc.numel() or word.numel() != doc.numel():
+        raise ValueError("expect_sides: doc [n], word [n] and grow [n, F]")
+    V, R, K = (int(x) for x in phi.shape)
+    n, F = (int(x) for x in grow.shape)
+    dev = theta.device
+    order = order.reshape(-1).to(torch.int64)
+    s0, e0 = seg_start.reshape(-1).to(torch.int64), seg_end.reshape(-1).to(torch.int64)
+    G = s0.numel()
+    if e0.numel() != G:
+        raise ValueError("expect_sides: seg_start and seg_end differ in length")
+    doc, word, g = doc.reshape(-1).to(torch.int64), word.reshape(-1).to(torch.int64), grow.reshape(-1).to(torch.int64)
+    best = torch.full((n * F,), -1, dtype=torch.int32, device=dev)
+    pbest = torch.full((n * F,), float("nan"), dtype=torch.float64, device=dev)
+    above = torch.full((n * F,), -1, dtype=torch.int32, device=dev)
+    out = lambda: (best.reshape(n, F), pbest.reshape(n, F), above.reshape(n, F))      # noqa: E731
+    if n == 0:
+        return out()
+    if int(doc.max()) >= theta.shape[0] or int(doc.min()) < -1 or int(word.max()) >= V or int(word.min()) < -1 \
+            or int(g.max()) >= G or int(g.min()) < -1:
+        raise ValueError("expect_sides: doc, word or grow out of range")
+    if G and (int(s0.min()) < 0 or int((e0 - s0).min()) < 0 or int(e0.max()) > order.numel()):
+        raise ValueError("expect_sides: segments outside the order")
+    if order.numel() and (int(order.min()) < 0 or int(order.max()) >= V):
+        raise ValueError("expect_sides: order out of range")
+    pair = torch.arange(n * F, device=dev, dtype=torch.int64) // F
+    items = torch.nonzero((g >= 0) & (word[pair] >= 0)).reshape(-1)
+    if items.numel() == 0:
+        return out()
+    lens = (e0 - s0)[g[items]]
+    above[items] = 0      # a group without members: -1, NaN, 0
+    ends = torch.cumsum(lens, 0).tolist()
+    i0, done = 0, 0
+    while i0 < items.numel():      # a slab: the items i0 .. i1 - 1
+        i1 = max(i0 + 1, bisect.bisect_right(ends, done + int(slab), i0))
+        it, ln = items[i0:i1], lens[i0:i1]
+        done, i0 = ends[i1 - 1], i1
+        tot = int(ln.sum())
+        if tot == 0:
+            continue
+        of = SG.segment_ids(ln, tot)                                    # the slab item of every member dot
+        first = torch.cumsum(ln, 0) - ln
+        v = order[s0[g[it]][of] + torch.arange(tot, device=dev) - first[of]]
+        d_it, w_it = doc[pair[it]], word[pair[it]]
+        i32 = lambda t: t.to(torch.int32)      # noqa: E731
+        p = score_ensemble(theta, phi, R, K, dflt, i32(d_it[of]), i32(v))[0]
+        s = score_ensemble(theta, phi, R, K, dflt, i32(d_it), i32(w_it))[0]
+        m = it.numel()
+        cnt = torch.zeros(m, dtype=torch.int64, device=dev).index_add_(0, of, (p > s[of]).to(torch.int64))
+        num = p == p
+        # the greatest p_v: -0.0 and +0.0 are one value; a slab item without a number keeps -inf and no row
+        pz = torch.where(p == 0, torch.zeros_like(p), p)
+        top = torch.full((m,), float("-inf"), dtype=torch.float64, device=dev)
+        top = top.scatter_reduce(0, of[num], pz[num], "amax", include_self=True)
+        win = num & (pz == top[of])
+        row = torch.full((m,), V, dtype=torch.int64, device=dev).scatter_reduce(0, of[win], v[win], "amin",
+                                                                               include_self=True)
+        has = row < V
+        at = win & (v == row[of])                                       # the winner (a row listed twice: one value)
+        pb = torch.full((m,), float("nan"), dtype=torch.float64, device=dev)
+        pb[of[at]] = p[at]
+        best[it] = torch.where(has, row, torch.full_like(row, -1)).to(torch.int32)
+        pbest[it] = pb
+        above[it] = cnt.to(torch.int32)
+    return out()
+
+
 TAIL_SLAB = 1 << 22      # doubles of the [sides, V] slab the tail twin holds at a time
 
 

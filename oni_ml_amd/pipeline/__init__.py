@@ -11,6 +11,9 @@ def run(cfg, dist=None, device=None, log=print) -> dict:
     if cfg.ensemble > 1 and dist is not None and dist.active:
         from ..config import ENSEMBLE_ONE_PROCESS
         raise ValueError(ENSEMBLE_ONE_PROCESS)
+    if cfg.expect and dist is not None and dist.active:
+        from ..config import EXPECT_ONE_PROCESS
+        raise ValueError(EXPECT_ONE_PROCESS)
     if cfg.explain and dist is not None and dist.active:
         from ..config import EXPLAIN_ONE_PROCESS
         raise ValueError(EXPLAIN_ONE_PROCESS)

@@ -601,13 +601,16 @@ def load_word_fields(lpath: str):
         return z["keys"].astype(np.int64), fields
 
 
-def write_explain(cfg, tables, order, key, sides, ex: ExplainInput, cols, sep: str = ",", log=print) -> dict:
+def write_explain(cfg, tables, order, key, sides, ex: ExplainInput, cols, sep: str = ",", log=print,
+                  keep: Optional[dict] = None) -> dict:
     """--explain: ``<type>_explain.csv`` next to the results file, line i describing its line i (``order``: the
     written events; ``cols``: their ``row_cols``): the key score, then per side the document, the word, the side's
     score, ``why`` -- the explained field of the word with the lowest conditional probability c_f, empty when
     there is none -- and c_f of every explained field (empty for NaN).  c_f = s / m_f, m_f the side's score with
     the φ row replaced by the sum of the φ rows that agree with the word on every field but f
-    (``scorer.field_groups``, ``scorer.explain_sides``).  Returns the summary entries."""
+    (``scorer.field_groups``, ``scorer.explain_sides``).  Returns the summary entries.  ``keep`` (--expect): a dict
+    that receives what ``write_expect`` goes on from -- the sides' rows, the distinct words and their groups -- so
+    that the groups are computed once for both files."""
     from ..ops import native
     from ..ops import sortgroup as SG
     from ..score import scorer as S
@@ -630,8 +633,11 @@ def write_explain(cfg, tables, order, key, sides, ex: ExplainInput, cols, sep: s
         rows, inv = SG.unique(word, return_inverse=True)
         none = int(rows[0] < 0) if rows.numel() else 0      # the -1 of the sides without a φ row sorts first
         rows = rows[none:]
-        gsum, grow_u, sizes = S.field_groups(ex.model, torch.from_numpy(np.asarray(word_keys, np.int64)), fields,
-                                             rows)
+        seg = S.field_segments(int(S.model_tables3(ex.model)[1].shape[0]),
+                               torch.from_numpy(np.asarray(word_keys, np.int64)), fields, rows, dev)
+        gsum, grow_u, sizes = S.field_groups(ex.model, None, fields, rows, segments=seg)
+        if keep is not None:
+            keep.update(doc=doc, word=word, rows=rows, seg=seg)
         if rows.numel():
             largest = sizes.max(0).values.cpu().tolist()
         if rows.numel():
@@ -659,6 +665,88 @@ def write_explain(cfg, tables, order, key, sides, ex: ExplainInput, cols, sep: s
     log(f"{cfg.dsource}_post: {n_sides * n} sides explained in {out}")
     return dict(explain_fields=names, explain_why_hist=dict(zip(names + ["none"], hist.astype(np.int64).tolist())),
                 explain_max_group=dict(zip(names, (int(x) for x in largest))))
+
+
+def write_expect(cfg, tables, order, key, sides, ex: ExplainInput, cols, kept: dict, sep: str = ",",
+                 log=print) -> dict:
+    """--expect: ``<type>_expect.csv`` next to the results file, line i describing its line i (``order``: the written
+    events; ``cols``: their ``row_cols``): the key score, then per side the document, the word, the side's score and
+    per explained field ``expected_f``, ``lift_f`` and ``above_f``.  With N_f(w) the group of the side's word w --
+    the vocabulary's words that agree with w on every field but f -- and p_v the side's score with the word v in
+    place of w: ``expected_f`` is the word of N_f(w) with the greatest p_v, by the name the results file gives it
+    (ties to the lowest φ row), ``lift_f`` = its p_v over the side's own score, one rounded division (>= 1; 1.0:
+    the event has the host's usual value there), ``above_f`` the number of words of N_f(w) with p_v above the
+    side's.  Cells are empty where there is no value.  The values depend on the pair (document, word) only: the
+    distinct pairs of the written sides are evaluated (``scorer.expect_sides``) and gathered.  ``kept``: what
+    ``write_explain`` left (the sides' rows and the groups).  Returns the summary entries."""
+    from ..ops import native
+    from ..ops import sortgroup as SG
+    from ..score import scorer as S
+    _, fields = tables.word_fields
+    names = [n for n, _, e in fields if e]
+    F = len(names)
+    dev = key.device
+    n = int(order.size)
+    o_t = torch.from_numpy(order).to(dev)
+    n_sides = len(ex.words)
+    V = int(S.model_tables3(ex.model)[1].shape[0])
+    best = np.full((n_sides * n, F), -1, np.int64)
+    above = np.full((n_sides * n, F), -1, np.int64)
+    lift = np.full((n_sides * n, F), np.nan)
+    pairs, dots = 0, 0
+    path = "cpu" if dev.type != "cuda" else S.expect_form()
+    if n and kept.get("rows") is not None and kept["rows"].numel():
+        doc, word, rows, seg = kept["doc"], kept["word"], kept["rows"], kept["seg"]
+        ok = word >= 0
+        # a pair: (document or none, word); a side without a document takes the default vector, so it has values
+        pk, inv = SG.unique(torch.where(ok, (doc + 1) * V + word, torch.full_like(doc, -1)), return_inverse=True)
+        none = int(pk[0] < 0)      # the -1 of the sides without a φ row sorts first
+        pk = pk[none:]
+        pairs = int(pk.numel())
+        if pairs:
+            pd = pk // V
+            pw = pk - pd * V
+            at_row = torch.searchsorted(rows, pw)      # ``rows``: the distinct words, ascending
+            grow = SG.gather(seg.grow, at_row)
+            dots = int(SG.gather(seg.sizes, at_row).sum())
+            (b_u, p_u, a_u), path = S.expect_sides(ex.model, seg, pd - 1, pw, grow)
+            at = (inv - none).clamp_min(0).cpu().numpy()
+            ok_h = ok.cpu().numpy()[:, None]
+            s_h = np.concatenate([SG.gather(sides[2 * j + 1], o_t).cpu().numpy() for j in range(n_sides)])
+            best = np.where(ok_h, b_u.cpu().numpy().astype(np.int64)[at], -1)
+            above = np.where(ok_h, a_u.cpu().numpy().astype(np.int64)[at], -1)
+            with np.errstate(invalid="ignore", divide="ignore"):
+                lift = np.where(ok_h, p_u.cpu().numpy()[at] / s_h[:, None], np.nan)      # one rounded division
+    out_cols = [("java", SG.gather(key, o_t).cpu().numpy())]
+    ub, b_inv = np.unique(best[best >= 0], return_inverse=True)      # the words named, once each
+    b_idx = np.full(best.shape, -1, np.int32)
+    b_idx[best >= 0] = b_inv.astype(np.int32)
+    b_names = [tables.word_names[i] for i in ub.tolist()]
+    ua, a_inv = np.unique(above[above >= 0], return_inverse=True)
+    a_idx = np.full(above.shape, -1, np.int32)
+    a_idx[above >= 0] = a_inv.astype(np.int32)
+    a_text = [str(int(x)) for x in ua]
+    for j in range(n_sides):
+        ip_names, ip_ids = ex.ips[j]
+        sl = slice(j * n, (j + 1) * n)
+        out_cols += [("dict", ip_names, SG.gather(ip_ids, o_t).cpu().numpy().astype(np.int32)),
+                     cols[ex.cols[j][0]], cols[ex.cols[j][1]]]
+        for f in range(F):
+            # a column's own lifts as its dictionary: the writer takes a dictionary in whole for every column
+            col = np.ascontiguousarray(lift[sl, f], np.float64)
+            have = ~np.isnan(col)
+            l_idx = np.full(n, -1, np.int32)
+            l_idx[have] = np.arange(int(have.sum()), dtype=np.int32)
+            out_cols += [("dict", b_names, np.ascontiguousarray(b_idx[sl, f])),
+                         ("dict", native.lib().java_double_array(col[have]), l_idx),
+                         ("dict", a_text, np.ascontiguousarray(a_idx[sl, f]))]
+    out = os.path.join(cfg.lpath, f"{cfg.dsource}_expect.csv")
+    native.lib().write_rows(out, None, out_cols, sep=sep, threads=cfg.threads, n=n)
+    modal = (above == 0).sum(0).astype(np.int64).tolist()
+    log(f"{cfg.dsource}_post: {n_sides * n} sides' expected values in {out} ({pairs} pairs, {dots} member dots x "
+        f"{ex.model.K} topics, {path})")
+    return dict(expect_fields=names, expect_modal_hist=dict(zip(names, modal)), expect_pairs=pairs,
+                expect_member_dots=dots, expect_path=path)
 
 
 @dataclass
@@ -839,7 +927,8 @@ def write_results(cfg, tables, what: str, ranked, key, row_cols, events: int, si
     ``doc_a, score_a, doc_b, score_b`` of ``write_host_report``) and the votes histogram.  Several ranks
     (``ctx``): the ranks' rows merged into one ascending file (``shardio.merge_sorted_rows``, the sortByKey
     shuffle), the counts summed.  ``extra``: further result entries.  ``explain``: the sides' φ rows and columns
-    for ``write_explain`` and ``write_tail`` (one process, under --explain / --tail).  ``tail_rank`` (--tail-tol):
+    for ``write_explain``, ``write_expect`` and ``write_tail`` (one process, under --explain / --expect / --tail).
+    ``tail_rank`` (--tail-tol):
     what ``tail_keys`` returned -- ``ranked`` was made from its key and flag, ``key`` stays the score key that the
     files' columns hold."""
     from ..ops import native
@@ -865,11 +954,14 @@ def write_results(cfg, tables, what: str, ranked, key, row_cols, events: int, si
     else:
         log(f"{cfg.dsource}_post: {flagged_text(n, below, limit, what, cfg.tol)} written to {out}")
     hosts = write_host_report(cfg, tables, *sides, row_cols, sep=sep, log=log) if cfg.host_report else {}
-    why = write_explain(cfg, tables, order, key, sides, explain, cols, sep=sep, log=log) if cfg.explain else {}
+    kept = {} if cfg.expect else None      # --expect goes on from the explain file's sides and groups
+    why = write_explain(cfg, tables, order, key, sides, explain, cols, sep=sep, log=log,
+                        keep=kept) if cfg.explain else {}
+    exp = write_expect(cfg, tables, order, key, sides, explain, cols, kept, sep=sep, log=log) if cfg.expect else {}
     tail = write_tail(cfg, tables, order, key, sides, explain, cols, sep=sep, log=log,
                       rank=tail_rank) if cfg.tail else {}
     return dict(flagged=n, below_tol=below, events=events, **(extra or {}), **hosts,
-                **votes_hist(votes, order, cfg.ensemble), **why, **tail,
+                **votes_hist(votes, order, cfg.ensemble), **why, **exp, **tail,
                 **(tail_rank.stats if tail_rank is not None else {}))
 
 

@@ -164,6 +164,11 @@ def run_stages(cfg, spec: PipelineSpec, device=None, log=print) -> dict:
                     why = {k: res[k] for k in ("explain_fields", "explain_why_hist", "explain_max_group")}
                     summary.update(why)
                     R.emit(dict(stage=post_stage + "_detail", **why))
+                if cfg.expect:
+                    exp = {k: res[k] for k in ("expect_fields", "expect_modal_hist", "expect_pairs",
+                                               "expect_member_dots", "expect_path")}
+                    summary.update(exp)
+                    R.emit(dict(stage=post_stage + "_detail", **exp))
                 if cfg.tail:
                     tail = {k: res[k] for k in ("tail_words", "tail_pairs", "tail_hist", "tail_total_range")}
                     if cfg.tail_tol is not None:      # flagged and ranked by the tail: what that took

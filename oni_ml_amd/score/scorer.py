@@ -182,20 +182,27 @@ def model_tables3(model):
     return model.theta.unsqueeze(1), model.phi.unsqueeze(1)
 
 
-def field_groups(model, word_keys: torch.Tensor, fields, rows: torch.Tensor):
-    """--explain: for the φ rows ``rows`` (int64, distinct, >= 0) and every explained field of ``fields``
-    (``WordSpace.fields()``: (name, radix, explained), most significant digit first), the sum of φ over the row's
-    group -- the φ rows whose key (``word_keys`` int64 [V], φ-row order) agrees with the row's on every digit but
-    that field's.  Returns ``(gsum [Gtot, R, K], grow int64 [len(rows), F], sizes int64 [len(rows), F])``:
-    ``grow[i, f]`` the ``gsum`` row of ``rows[i]``'s group of the f-th explained field, ``sizes`` its members.
+@dataclass
+class FieldSegments:
+    """The groups of ``field_segments``: the explained fields' stable sorts back to back (``order`` int32 [F V]),
+    the referenced groups' segments of it (``seg_start`` / ``seg_end`` int64 [Gtot]), and per given row the group
+    of every explained field (``grow`` int64 [len(rows), F]) with its size (``sizes``)."""
+    order: torch.Tensor
+    seg_start: torch.Tensor
+    seg_end: torch.Tensor
+    grow: torch.Tensor
+    sizes: torch.Tensor
 
-    On the device, from ``ops/sortgroup.py`` primitives only: per field one stable int64 sort of the V masked
-    keys (ties keep row order), the runs' starts, and the segments the given rows reference -- at most
-    len(rows) x F group sums are made, never V x K per field."""
+
+def field_segments(V: int, word_keys: torch.Tensor, fields, rows: torch.Tensor, device) -> FieldSegments:
+    """For the φ rows ``rows`` (int64, distinct, >= 0) and every explained field of ``fields``
+    (``WordSpace.fields()``: (name, radix, explained), most significant digit first), the row's group: the φ rows
+    whose key (``word_keys`` int64 [V], φ-row order) agrees with the row's on every digit but that field's, the row
+    among them.  On the device, from ``ops/sortgroup.py`` primitives only: per field one stable int64 sort of the V
+    masked keys (ties keep row order, so a group's members ascend by row), the runs' starts, and the segments the
+    given rows reference.  What --explain sums (``field_groups``) and --expect walks (``expect_sides``)."""
     from ..ops import sortgroup as SG
-    theta, phi = model_tables3(model)
-    V, R, K = phi.shape
-    dev = phi.device
+    dev = device
     if word_keys.numel() != V:
         raise ValueError(f"field_groups: {word_keys.numel()} word keys for {V} phi rows")
     radix = [int(r) for _, r, _ in fields]
@@ -203,7 +210,6 @@ def field_groups(model, word_keys: torch.Tensor, fields, rows: torch.Tensor):
     for i in range(len(fields) - 2, -1, -1):
         stride[i] = stride[i + 1] * radix[i + 1]
     keys = word_keys.to(dev).to(torch.int64)
-    flat = phi.reshape(V, R * K)
     orders, starts, ends, grows, sizes, base = [], [], [], [], [], 0
     for i, (_, r, explained) in enumerate(fields):
         if not explained:
@@ -227,9 +233,25 @@ def field_groups(model, word_keys: torch.Tensor, fields, rows: torch.Tensor):
         base += int(ug.numel())
     if not orders:
         raise ValueError("field_groups: no explained field")
+    return FieldSegments(torch.cat(orders), torch.cat(starts), torch.cat(ends), torch.stack(grows, 1),
+                         torch.stack(sizes, 1))
+
+
+def field_groups(model, word_keys: torch.Tensor, fields, rows: torch.Tensor, segments: Optional[FieldSegments] = None):
+    """--explain: for the φ rows ``rows`` (int64, distinct, >= 0) and every explained field of ``fields``
+    (``WordSpace.fields()``: (name, radix, explained), most significant digit first), the sum of φ over the row's
+    group -- the φ rows whose key (``word_keys`` int64 [V], φ-row order) agrees with the row's on every digit but
+    that field's.  Returns ``(gsum [Gtot, R, K], grow int64 [len(rows), F], sizes int64 [len(rows), F])``:
+    ``grow[i, f]`` the ``gsum`` row of ``rows[i]``'s group of the f-th explained field, ``sizes`` its members.
+
+    The groups are ``field_segments``' (``segments``: what it returned for these arguments, when the caller has
+    it) -- at most len(rows) x F group sums are made, never V x K per field."""
+    theta, phi = model_tables3(model)
+    V, R, K = phi.shape
+    seg = segments if segments is not None else field_segments(V, word_keys, fields, rows, phi.device)
     # one launch pair (and one set of host-side bound checks) for every field's groups
-    gsum = group_rows_sum(flat, torch.cat(orders), torch.cat(starts), torch.cat(ends)).reshape(-1, R, K)
-    return gsum, torch.stack(grows, 1), torch.stack(sizes, 1)
+    gsum = group_rows_sum(phi.reshape(V, R * K), seg.order, seg.seg_start, seg.seg_end).reshape(-1, R, K)
+    return gsum, seg.grow, seg.sizes
 
 
 def explain_sides(model, gsum: torch.Tensor, doc: torch.Tensor, word: torch.Tensor, grow: torch.Tensor):
@@ -242,6 +264,30 @@ def explain_sides(model, gsum: torch.Tensor, doc: torch.Tensor, word: torch.Tens
     else:
         from ..ops.reference import explain_sides as fn
     return fn(theta.contiguous(), phi.contiguous(), gsum.contiguous(), i32(doc), i32(word), i32(grow), model.default)
+
+
+def expect_sides(model, seg: FieldSegments, doc: torch.Tensor, word: torch.Tensor, grow: torch.Tensor):
+    """``((best int32 [n, F], pbest float64 [n, F], above int32 [n, F]), path)`` of (document, word) pairs: per
+    explained field the member of the word's group (``seg``: ``field_segments``; ``grow`` [n, F] its groups or -1)
+    that the document's model finds most probable, that member's score and the number of members that beat the
+    word itself.  ``path``: ``"blocks"`` (``ops.hip.expect_sides``) on the GPU, ``"cpu"`` (its torch twin: the same
+    bits) elsewhere; ``model``: a TopicModel or an EnsembleModel."""
+    theta, phi = model_tables3(model)
+    i32 = lambda t: t.to(torch.int32).contiguous()      # noqa: E731
+    i64 = lambda t: t.to(torch.int64).contiguous()      # noqa: E731
+    args = (theta.contiguous(), phi.contiguous(), i32(seg.order), i64(seg.seg_start), i64(seg.seg_end), i32(doc),
+            i32(word), i32(grow), model.default)
+    if theta.device.type == "cuda":
+        from ..ops import hip as H
+        return H.expect_sides(*args), H.EXPECT_FORMS[0]
+    from ..ops.reference import expect_sides as ref
+    return ref(*args), "cpu"
+
+
+def expect_form() -> str:
+    """The form of ``ops.hip.expect_sides`` that runs on the GPU (``expect_path`` of a run without a pair)."""
+    from ..ops.hip import EXPECT_FORMS
+    return EXPECT_FORMS[0]
 
 
 def tail_mass(model, doc: torch.Tensor, word: torch.Tensor):
