@@ -240,6 +240,15 @@ PYBIND11_MODULE(_onihip, m) {
     oni::launch_tail_docs(a, max_blocks, S(stream));
   });
 
+  m.def("peers_max", []() { return oni::kPeersMax; });
+  m.def("peer_theta_path", [](int R, int K) { return oni::peer_theta_path(R, K); });
+  m.def("peer_topn", [](u theta, int W, int64_t D, u query, int64_t n, int N, int64_t block, int64_t nblk, u scratch,
+                        u rows, u dist, u count, int max_blocks, u stream) {
+    oni::PeerArgs a{P<const double>(theta), W, D, P<const int>(query), n, N, block, nblk, P<double>(scratch),
+                    P<int>(rows), P<double>(dist), P<int>(count)};
+    oni::launch_peer_topn(a, max_blocks, S(stream));
+  });
+
   m.def("holdout_draw", [](u base, u counts, u chunk_off, int64_t nnz, int64_t chunks, unsigned long long key,
                            unsigned long long thr, int lane_tokens, u t, int max_blocks, u stream) {
     oni::HoldoutDrawArgs a{P<const int64_t>(base), P<const int64_t>(counts), P<const int64_t>(chunk_off), nnz, chunks,

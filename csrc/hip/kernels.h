@@ -399,6 +399,34 @@ int tail_theta_path(int R, int K);   // the TailPath the launch takes at this ro
 // row) instead of once per pair.  Only where tail_theta_path(R, K) == kTailRegisters; any other width throws.
 void launch_tail_docs(const TailArgs& a, int max_blocks, hipStream_t s);
 
+// --peers (peers.hip).  Rows of theta are W = R K doubles.  L(q, p) = the L1 distance of rows q and p: from 0.0, for
+// j = 0 .. W - 1 in order, t = theta[q][j] - theta[p][j] (one rounded subtraction), acc = acc + |t| (one rounded add).
+// For query i the N candidates p != query[i] lowest in the total order (L, p), a NaN L never among them, in that
+// order: rows[i][0 .. count[i]) and dist[i][..]; the slots past count[i] hold -1 and +inf.  The top N of a set under
+// a total order does not depend on how the set is cut: the same bits for every grid, block and batch, no atomics.
+constexpr int kPeersMax = 16;   // largest N
+enum PeerPath : int {
+  kPeerRegisters = 0,   // the query's row in registers (padded to a compiled width of at most 100 doubles)
+  kPeerDirect = 1,      // both rows read from global memory
+};
+struct PeerArgs {
+  const double* theta;   // [D][W]
+  int W;                 // doubles of a row, >= 1
+  int64_t D;             // rows, 0 <= D < 2^31
+  const int* query;      // [n] rows, 0 <= query[i] < D (bounds checked on the host)
+  int64_t n;             // 0 <= n < 2^31
+  int N;                 // 1 <= N <= kPeersMax
+  int64_t block;         // candidate rows of a block, >= 1
+  int64_t nblk;          // ceil(D / block)
+  double* scratch;       // nblk * n * N * 12 bytes: [nblk][N][n] doubles (L), then [nblk][N][n] ints (row)
+  int* rows;             // [n][N]
+  double* dist;          // [n][N]
+  int* count;            // [n]
+};
+// max_blocks: cap on the workgroups per launch (0: 65536)
+void launch_peer_topn(const PeerArgs& a, int max_blocks, hipStream_t s);
+int peer_theta_path(int R, int K);   // the PeerPath the launch takes at this row shape
+
 // --holdout (holdout.hip).  holdout_draw: t[e] = the tokens j of CSR entry e, 0 <= j < counts[e], with
 // splitmix64(key ^ (base[e] + j)) >> 11 < thr -- integers only, so t depends on nothing but (key, thr, corpus).
 // An entry of at most lane_tokens tokens is drawn by one lane; a longer one is cut into chunks of

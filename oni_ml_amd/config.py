@@ -27,7 +27,7 @@ from .models.lda.settings import LDASettings
 
 ENV_KEYS = ("FLOW_PATH", "DNS_PATH", "PROXY_PATH", "HPATH", "LPATH", "LUSER", "TOL", "DUPFACTOR", "KRB_AUTH", "NODES",
             "UINODE", "RPATH", "LDAPATH", "SPK_EXEC", "SPK_EXEC_MEM", "TOP1M", "CUT", "MAXRESULTS", "ENSEMBLE", "EXPLAIN",
-            "HOLDOUT", "HOLDOUT_TOPICS", "TAIL", "TAIL_TOL", "EXPECT")
+            "HOLDOUT", "HOLDOUT_TOPICS", "TAIL", "TAIL_TOL", "EXPECT", "PEERS")
 
 # proxy has no multi-rank, sharded or HDFS-staged form
 PROXY_ONE_PROCESS = "proxy runs on one process: launch it without torchrun, with --gpus 1 and without --hdfs"
@@ -64,6 +64,16 @@ TAIL_SCRATCH_MB = 256      # cap on the per-block partials of one launch of ops.
 # only.  Measured on an MI355X at 1 / 2 / 4 / 8 / 16 pairs per document (profiles/tail_rank.md section 2): at 1 the
 # shared-vector kernel loses (49 ms against 33 ms), from 2 on it wins (27 ms against 33 ms)
 TAIL_DOCS_MIN_SHARE = 2.0
+
+# the peers files are made from one process's written sides and its whole theta table: no multi-rank, sharded or
+# HDFS-staged form
+PEERS_ONE_PROCESS = "--peers runs on one process: launch it without torchrun, with --gpus 1 and without --hdfs"
+PEERS_MAX = 16             # largest N of --peers (csrc/hip/kernels.h kPeersMax)
+# candidate rows of one block of ops.hip.peer_topn and the cap on its per-block lists (N x 12 bytes per query and
+# block; more queries: batches).  Neither changes a bit of the result: the values move time only (measured on an
+# MI355X: profiles/peers.md)
+PEERS_BLOCK = 4096
+PEERS_SCRATCH_MB = 256
 
 # --holdout: the split and the K fits are one process's: no multi-rank, sharded or HDFS-staged form
 HOLDOUT_ONE_PROCESS = "--holdout runs on one process: launch it without torchrun, with --gpus 1 and without --hdfs"
@@ -140,6 +150,9 @@ class RunConfig:
     tail_tol: Optional[float] = None      # --tail-tol / TAIL_TOL: flag and rank the events by their tail p-value, the
                                           # lower of the sides' tails, under this threshold (0 < P <= 1; implies
                                           # tail); None: by the score under TOL, as ever
+    peers: int = 0                        # --peers / PEERS: also write <type>_peers.csv and <type>_peer_groups.csv,
+                                          # every written side scored at its host's N nearest hosts in topic space
+                                          # (1 <= N <= PEERS_MAX); 0: off
     holdout: float = 0.0                  # --holdout / HOLDOUT: hold this fraction of every document's tokens out, fit
                                           # on the rest and report the held-out perplexity per topic count; 0: off
     holdout_topics: str = ""              # --holdout-topics / HOLDOUT_TOPICS: "K1,K2,..." to evaluate; "": topics alone
@@ -227,6 +240,7 @@ class RunConfig:
             self.tail = True      # the tail file describes the rows the threshold chose
         if self.tail and (self.gpus > 1 or self.hdfs):
             raise ValueError(TAIL_ONE_PROCESS)
+        self.peers = self.check_peers(self.peers, self.gpus, self.hdfs)
         self.check_ensemble(self.ensemble, self.start, self.gpus, self.hdfs)
         self.check_holdout(self.holdout, self.holdout_list(), self.holdout_select, self.start, self.compat,
                            self.dsource, self.backend, self.gpus, self.hdfs)
@@ -243,6 +257,18 @@ class RunConfig:
         if not 0.0 < p <= 1.0:      # (a NaN fails both comparisons)
             raise ValueError(f"--tail-tol must be in (0, 1], got {p}")
         return p
+
+    @staticmethod
+    def check_peers(n, gpus: int = 1, hdfs: bool = False, world: int = 1) -> int:
+        """The --peers rules, also applied by the command line before anything is written."""
+        n = int(n)
+        if n == 0:
+            return 0
+        if not 1 <= n <= PEERS_MAX:
+            raise ValueError(f"--peers must be 0 (off) or in [1, {PEERS_MAX}], got {n}")
+        if gpus > 1 or hdfs or world > 1:
+            raise ValueError(PEERS_ONE_PROCESS)
+        return n
 
     @staticmethod
     def check_holdout(holdout: float, topics: List[int], select: bool, start: str, compat: str, dsource: str,
@@ -352,6 +378,8 @@ def _apply(cfg: RunConfig, layer: Dict[str, object]):
         cfg.tail = str(layer["TAIL"]).strip().lower() not in ("0", "false", "no", "off")
     if "TAIL_TOL" in layer and layer["TAIL_TOL"] not in ("", None):
         cfg.tail_tol = float(layer["TAIL_TOL"])
+    if "PEERS" in layer and layer["PEERS"] not in ("", None):
+        cfg.peers = int(layer["PEERS"])
     if "HOLDOUT" in layer and layer["HOLDOUT"] not in ("", None):
         cfg.holdout = float(layer["HOLDOUT"])
     if "HOLDOUT_TOPICS" in layer and layer["HOLDOUT_TOPICS"] not in ("", None):

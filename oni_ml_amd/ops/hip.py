@@ -835,6 +835,80 @@ def _tail_launch(who, docs, theta, phi, doc, word, block, max_blocks, scratch_mb
     return le, tot, rarer, ties
 
 
+PEER_PATHS = ("registers", "direct")
+
+
+def peer_theta_path(R: int, K: int) -> str:
+    """Which form of the peers kernel a row of R members x K topics takes (csrc/hip/peers.hip): the query's row in
+    ``registers`` (R K <= 100) or both rows read from global memory (``direct``)."""
+    return PEER_PATHS[lib().peer_theta_path(int(R), int(K))]
+
+
+def peer_topn(theta3, query, n, block=None, max_blocks: int = 0, scratch_mb=None):
+    """The ``n`` nearest rows of every query row in L1 distance (csrc/hip/peers.hip; ``ops.reference.peer_topn`` is
+    the twin): ``(rows int32 [Q, n], dist float64 [Q, n], count int32 [Q])`` as new device tensors.
+
+    ``theta3`` [D, R, K], its rows W = R K doubles; ``query`` int32 [Q] rows.  L(q, p): from 0.0, for j = 0 .. W - 1
+    in order, one rounded subtraction and one rounded add of its magnitude.  Listed are the candidates p != q lowest
+    in the order (L, p) ascending, a NaN L never; ``count`` of them, the slots past it -1 and +inf.  The same bits
+    for every grid, ``block`` (``config.PEERS_BLOCK`` candidate rows) and batch; no atomics.
+
+    The per-block lists (n x 12 bytes per query and block) live in a scratch of at most ``scratch_mb`` MiB
+    (``config.PEERS_SCRATCH_MB``): more queries than fit are processed in batches.  Everything is checked on the
+    host before the launch; ``Q == 0`` launches nothing.  ``max_blocks``: cap on the workgroups per launch (tests: a
+    small cap makes the grid-stride loops wrap)."""
+    import operator
+    _max_blocks(max_blocks)
+    PB = operator.index(_CFG.PEERS_BLOCK if block is None else block)
+    if PB < 1:
+        raise ValueError(f"peer_topn: block must be >= 1, got {PB}")
+    cap_mb = float(_CFG.PEERS_SCRATCH_MB if scratch_mb is None else scratch_mb)
+    if not cap_mb > 0:
+        raise ValueError(f"peer_topn: scratch_mb must be > 0, got {scratch_mb!r}")
+    N = operator.index(n)
+    if not 1 <= N <= _CFG.PEERS_MAX:
+        raise ValueError(f"peer_topn: n must be in [1, {_CFG.PEERS_MAX}], got {N}")
+    if not isinstance(theta3, torch.Tensor) or theta3.dim() != 3:
+        raise ValueError("theta: expected a [rows, R, K] tensor")
+    D, R, K = (int(x) for x in theta3.shape)
+    if R < 1 or K < 1 or R * K >= 1 << 31:
+        raise ValueError(f"peer_topn: R and K must be >= 1 and R K < 2^31, got {R} x {K}")
+    _table3("theta", theta3, R, K)
+    dev = theta3.device
+    if D >= 1 << 31 or PB >= 1 << 31:
+        raise ValueError(f"peer_topn: {D} theta rows, block {PB} (both < 2^31)")
+    if not isinstance(query, torch.Tensor) or query.dim() != 1:
+        raise ValueError("query: expected a 1-D tensor")
+    Q = query.numel()
+    if Q >= 1 << 31:
+        raise ValueError(f"peer_topn: {Q} queries (Q < 2^31)")
+    _index("query", query, torch.int32, (Q,), dev)
+    rows = torch.empty((Q, N), dtype=torch.int32, device=dev)
+    dist = torch.empty((Q, N), dtype=torch.float64, device=dev)
+    count = torch.empty(Q, dtype=torch.int32, device=dev)
+    if Q == 0:
+        return rows, dist, count
+    # index bounds (host check before a kernel touches memory)
+    if int(query.max()) >= D or int(query.min()) < 0:
+        raise ValueError("query: index out of range")
+    L = lib()
+    if L.peers_max() != _CFG.PEERS_MAX:
+        raise RuntimeError("peer_topn: config.PEERS_MAX differs from the compiled limit")
+    nblk = -(-D // PB)
+    per_query = 12 * N * nblk
+    batch = max(1, min(Q, int(cap_mb * (1 << 20)) // per_query))
+    if batch < Q and batch >= 256:
+        batch -= batch % 256      # whole tiles of queries
+    # doubles first, then ints: [nblk][N][batch] of each, rounded up to whole doubles
+    scratch = torch.empty(batch * nblk * N + (batch * nblk * N + 1) // 2, dtype=torch.float64, device=dev)
+    for s0 in range(0, Q, batch):
+        m = min(batch, Q - s0)
+        L.peer_topn(theta3.data_ptr(), R * K, D, query.data_ptr() + 4 * s0, int(m), N, int(PB), int(nblk),
+                    scratch.data_ptr(), rows.data_ptr() + 4 * N * s0, dist.data_ptr() + 8 * N * s0,
+                    count.data_ptr() + 4 * s0, int(max_blocks), _stream())
+    return rows, dist, count
+
+
 def holdout_draw(doc_ptr, counts, seed, thr, max_blocks: int = 0, rules: bool = True, lane_tokens=None):
     """Held-out tokens of every CSR entry (csrc/hip/holdout.hip; ``ops.reference.holdout_draw`` is the twin): int64
     [nnz] as a new device tensor.

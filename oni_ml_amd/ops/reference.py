@@ -395,6 +395,54 @@ def tail_mass(theta, phi, doc, word, block=None, slab: int = TAIL_SLAB):
     return le, tot, rarer, ties
 
 
+PEERS_SLAB = 1 << 22      # doubles of the [queries, D] slab the peers twin holds at a time
+
+
+def peer_topn(theta3, query, n, slab: int = PEERS_SLAB):
+    """Torch twin of ``ops.hip.peer_topn`` (csrc/hip/peers.hip) on any device, bit for bit, and the CPU pipeline's
+    path: ``(rows int32 [Q, n], dist float64 [Q, n], count int32 [Q])``.  ``theta3`` [D, R, K], its rows W = R K
+    doubles; ``query`` [Q] rows.  L(q, p) is the L1 distance of rows q and p: from 0.0, for j = 0 .. W - 1 in order,
+    ``t = theta[q, j] - theta[p, j]`` and ``acc = acc + |t|``, each rounded once.  The peers of q are the ``n``
+    candidates p != q lowest in the order (L, p) ascending, listed in that order; a NaN L is never a peer;
+    ``count`` is the number found, the slots past it hold -1 and +inf.  Queries are taken in batches of at most
+    ``slab`` / D: a loop over j, then a stable ascending sort (equal distances stay in row order, torch puts NaN
+    last), the query's own row made NaN first."""
+    from ..config import PEERS_MAX
+    n = int(n)
+    if not 1 <= n <= PEERS_MAX:
+        raise ValueError(f"peer_topn: n must be in [1, {PEERS_MAX}], got {n}")
+    if theta3.dim() != 3 or theta3.dtype != torch.float64:
+        raise ValueError("peer_topn: theta [D, R, K] float64")
+    q = query.reshape(-1).to(torch.int64)
+    D = int(theta3.shape[0])
+    Q = q.numel()
+    dev = theta3.device
+    rows = torch.full((Q, n), -1, dtype=torch.int32, device=dev)
+    dist = torch.full((Q, n), float("inf"), dtype=torch.float64, device=dev)
+    count = torch.zeros(Q, dtype=torch.int32, device=dev)
+    if Q == 0:
+        return rows, dist, count
+    if int(q.max()) >= D or int(q.min()) < 0:
+        raise ValueError("peer_topn: query out of range")
+    th = theta3.reshape(D, -1)
+    m = min(n, D)
+    step = max(1, int(slab) // D)
+    for b0 in range(0, Q, step):
+        qs = q[b0:b0 + step]
+        own = th[qs]                                                    # [m, W]
+        acc = torch.zeros((qs.numel(), D), dtype=torch.float64, device=dev)
+        for j in range(th.shape[1]):
+            acc = acc + (own[:, j].unsqueeze(1) - th[:, j].unsqueeze(0)).abs()      # rounded difference, rounded sum
+        acc[torch.arange(qs.numel(), device=dev), qs] = float("nan")    # the query itself is no candidate
+        sd, order = torch.sort(acc, dim=1, stable=True)
+        found = (sd == sd).sum(1).clamp_max(n)
+        live = torch.arange(m, device=dev).unsqueeze(0) < found.unsqueeze(1)
+        rows[b0:b0 + step, :m] = torch.where(live, order[:, :m], torch.full_like(order[:, :m], -1)).to(torch.int32)
+        dist[b0:b0 + step, :m] = torch.where(live, sd[:, :m], torch.full_like(sd[:, :m], float("inf")))
+        count[b0:b0 + step] = found.to(torch.int32)
+    return rows, dist, count
+
+
 def select_lowest(key, flag, limit, with_count: bool = False):
     """Torch twin of ``ops.hip.select_lowest`` (csrc/hip/select_lowest.hip) on any device: the row indices
     (int64, ascending) of the ``limit`` flagged rows that a stable ascending sort of their keys puts first, all

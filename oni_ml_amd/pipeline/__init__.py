@@ -20,6 +20,9 @@ def run(cfg, dist=None, device=None, log=print) -> dict:
     if cfg.tail and dist is not None and dist.active:
         from ..config import TAIL_ONE_PROCESS
         raise ValueError(TAIL_ONE_PROCESS)
+    if cfg.peers and dist is not None and dist.active:
+        from ..config import PEERS_ONE_PROCESS
+        raise ValueError(PEERS_ONE_PROCESS)
     if cfg.holdout > 0 and dist is not None and dist.active:
         from ..config import HOLDOUT_ONE_PROCESS
         raise ValueError(HOLDOUT_ONE_PROCESS)

@@ -889,6 +889,107 @@ def write_tail(cfg, tables, order, key, sides, ex: ExplainInput, cols, sep: str 
                 tail_hist=dict(zip(TAIL_DECADES + ("none",), hist.tolist() + [int(tail.size - good.size)])))
 
 
+PEER_LIFT_DECADES = ("<1e-2", "<1e-1", "<1", "<1e1", "<1e2", "<1e3", ">=1e3")
+
+
+def write_peers(cfg, tables, order, key, sides, ex: ExplainInput, cols, sep: str = ",", log=print) -> dict:
+    """--peers N: ``<type>_peers.csv`` next to the results file, line i describing its line i (``order``: the written
+    events; ``cols``: their ``row_cols``): the key score, then per side the document, the word, the side's score,
+    ``peers`` (how many of the document's N nearest documents were found), ``peer_dist`` (the L1 distance of the
+    farthest of them / (2 R): the total-variation distance averaged over the members), ``peer_score`` (the mean
+    score of the side's word at those peers, ``scorer.peer_scores``) and ``peer_lift`` = peer_score / the side's own
+    score, one rounded division.  A side without a document gets four empty cells, one without a φ row ``peers``
+    and ``peer_dist`` only.  And ``<type>_peer_groups.csv``: one line per distinct document of the written sides,
+    ascending by θ row: the host, its count, then N x (peer host, its distance / (2 R)), empty past the count.
+    The distinct documents are found with ``ops/sortgroup.py`` primitives and go through ``scorer.peer_topn`` once.
+    Returns the summary entries."""
+    from ..ops import native
+    from ..ops import sortgroup as SG
+    from ..score import scorer as S
+    dev = key.device
+    N = int(cfg.peers)
+    n = int(order.size)
+    o_t = torch.from_numpy(order).to(dev)
+    n_sides = len(ex.words)
+    theta = S.model_tables3(ex.model)[0]
+    D, R, K = (int(x) for x in theta.shape)
+    two_r = 2.0 * R
+    cnt = np.full(n_sides * n, -1, np.int64)
+    far = np.full(n_sides * n, np.nan)
+    ps = np.full(n_sides * n, np.nan)
+    lift = np.full(n_sides * n, np.nan)
+    ud = torch.zeros(0, dtype=torch.int64, device=dev)
+    if n:
+        doc = torch.cat([SG.gather(sides[2 * j], o_t).to(torch.int64) for j in range(n_sides)])
+        word = torch.cat([SG.gather(w, o_t).to(torch.int64) for w in ex.words])
+        ud, inv = SG.unique(doc, return_inverse=True)
+        none = int(ud[0] < 0)      # the -1 of the sides without a document sorts first
+        ud = ud[none:]
+    (rows_u, dist_u, cnt_u), path = S.peer_topn(ex.model, ud, N)
+    hosts = int(ud.numel())
+    if hosts:
+        has = doc >= 0
+        at = (inv - none).clamp_min(0)
+        cnt_s = torch.where(has, SG.gather(cnt_u, at).to(torch.int64), torch.zeros_like(doc))
+        dist_s = SG.gather(dist_u, at)
+        last = torch.gather(dist_s, 1, (cnt_s - 1).clamp_min(0).unsqueeze(1)).reshape(-1)
+        ps_t = S.peer_scores(ex.model, SG.gather(rows_u, at), cnt_s, doc, word)
+        s_h = np.concatenate([SG.gather(sides[2 * j + 1], o_t).cpu().numpy() for j in range(n_sides)])
+        has_h, cnt_h = has.cpu().numpy(), cnt_s.cpu().numpy()
+        cnt = np.where(has_h, cnt_h, -1)
+        ps = ps_t.cpu().numpy()
+        with np.errstate(invalid="ignore", divide="ignore"):
+            far = np.where(has_h & (cnt_h > 0), last.cpu().numpy() / two_r, np.nan)      # one rounded division each
+            lift = ps / s_h
+
+    def doubles(x):      # a column's own values as its dictionary, empty cells for NaN
+        x = np.ascontiguousarray(x, np.float64)
+        have = ~np.isnan(x)
+        idx = np.full(x.size, -1, np.int32)
+        idx[have] = np.arange(int(have.sum()), dtype=np.int32)
+        return ("dict", native.lib().java_double_array(x[have]), idx)
+
+    def ints(x):         # -1: an empty cell
+        ux, x_inv = np.unique(x[x >= 0], return_inverse=True)
+        idx = np.full(x.size, -1, np.int32)
+        idx[x >= 0] = x_inv.astype(np.int32)
+        return ("dict", [str(int(v)) for v in ux], idx)
+
+    out_cols = [("java", SG.gather(key, o_t).cpu().numpy())]
+    for j in range(n_sides):
+        ip_names, ip_ids = ex.ips[j]
+        sl = slice(j * n, (j + 1) * n)
+        out_cols += [("dict", ip_names, SG.gather(ip_ids, o_t).cpu().numpy().astype(np.int32)),
+                     cols[ex.cols[j][0]], cols[ex.cols[j][1]], ints(cnt[sl]), doubles(far[sl]), doubles(ps[sl]),
+                     doubles(lift[sl])]
+    out = os.path.join(cfg.lpath, f"{cfg.dsource}_peers.csv")
+    native.lib().write_rows(out, None, out_cols, sep=sep, threads=cfg.threads, n=n)
+    # the groups: one line per distinct document
+    ud_h = ud.cpu().numpy()
+    rows_h = rows_u.cpu().numpy().astype(np.int64).reshape(hosts, N)
+    dist_h = dist_u.cpu().numpy().reshape(hosts, N)
+    cnt_uh = cnt_u.cpu().numpy().astype(np.int64)
+    ur, r_inv = np.unique(rows_h[rows_h >= 0], return_inverse=True)      # the hosts named, once each
+    r_idx = np.full(rows_h.shape, -1, np.int32)
+    r_idx[rows_h >= 0] = r_inv.astype(np.int32)
+    r_names = [tables.doc_names[i] for i in ur.tolist()]
+    g_cols = [("dict", [tables.doc_names[d] for d in ud_h.tolist()], np.arange(hosts, dtype=np.int32)),
+              ("int", cnt_uh)]
+    for i in range(N):
+        g_cols += [("dict", r_names, np.ascontiguousarray(r_idx[:, i])),
+                   doubles(np.where(rows_h[:, i] >= 0, dist_h[:, i] / two_r, np.nan))]
+    g_out = os.path.join(cfg.lpath, f"{cfg.dsource}_peer_groups.csv")
+    native.lib().write_rows(g_out, None, g_cols, sep=sep, threads=cfg.threads, n=hosts)
+    good = lift[~np.isnan(lift)]
+    edges = np.asarray([1e-2, 1e-1, 1.0, 1e1, 1e2, 1e3])
+    hist = np.bincount(np.searchsorted(edges, good, side="right"), minlength=len(PEER_LIFT_DECADES)).astype(np.int64)
+    identical = int(((cnt_uh > 0) & (dist_h[:, 0] == 0.0)).sum()) if hosts else 0
+    log(f"{cfg.dsource}_post: {n_sides * n} sides scored at their hosts' {N} nearest hosts in {out}, the groups in "
+        f"{g_out} ({hosts} hosts x {D} candidates x {R * K} subtract-adds, {path})")
+    return dict(peers=N, peer_hosts=hosts, peer_candidates=D, peer_path=path, peer_identical=identical,
+                peer_lift_hist=dict(zip(PEER_LIFT_DECADES + ("none",), hist.tolist() + [int(lift.size - good.size)])))
+
+
 def one_sided_index(tables, ip_names, ip, unames, inv, device, ip_map=None):
     """The one-sided scorers' (dns, proxy) index set-up: (θ, φ, θ row of every event, φ row of every event).
     ``ip`` / ``inv``: every event's id into ``ip_names`` / ``unames``; ``ip_map``: the doc row of every ip id
@@ -927,7 +1028,8 @@ def write_results(cfg, tables, what: str, ranked, key, row_cols, events: int, si
     ``doc_a, score_a, doc_b, score_b`` of ``write_host_report``) and the votes histogram.  Several ranks
     (``ctx``): the ranks' rows merged into one ascending file (``shardio.merge_sorted_rows``, the sortByKey
     shuffle), the counts summed.  ``extra``: further result entries.  ``explain``: the sides' φ rows and columns
-    for ``write_explain``, ``write_expect`` and ``write_tail`` (one process, under --explain / --expect / --tail).
+    for ``write_explain``, ``write_expect``, ``write_tail`` and ``write_peers`` (one process, under --explain /
+    --expect / --tail / --peers).
     ``tail_rank`` (--tail-tol):
     what ``tail_keys`` returned -- ``ranked`` was made from its key and flag, ``key`` stays the score key that the
     files' columns hold."""
@@ -960,8 +1062,9 @@ def write_results(cfg, tables, what: str, ranked, key, row_cols, events: int, si
     exp = write_expect(cfg, tables, order, key, sides, explain, cols, kept, sep=sep, log=log) if cfg.expect else {}
     tail = write_tail(cfg, tables, order, key, sides, explain, cols, sep=sep, log=log,
                       rank=tail_rank) if cfg.tail else {}
+    peers = write_peers(cfg, tables, order, key, sides, explain, cols, sep=sep, log=log) if cfg.peers else {}
     return dict(flagged=n, below_tol=below, events=events, **(extra or {}), **hosts,
-                **votes_hist(votes, order, cfg.ensemble), **why, **exp, **tail,
+                **votes_hist(votes, order, cfg.ensemble), **why, **exp, **tail, **peers,
                 **(tail_rank.stats if tail_rank is not None else {}))
 
 

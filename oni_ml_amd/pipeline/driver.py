@@ -176,6 +176,11 @@ def run_stages(cfg, spec: PipelineSpec, device=None, log=print) -> dict:
                                                          "tail_rank_path", "tail_sides_skipped")})
                     summary.update(tail)
                     R.emit(dict(stage=post_stage + "_detail", **tail))
+                if cfg.peers:
+                    peers = {k: res[k] for k in ("peers", "peer_hosts", "peer_candidates", "peer_path",
+                                                 "peer_identical", "peer_lift_hist")}
+                    summary.update(peers)
+                    R.emit(dict(stage=post_stage + "_detail", **peers))
         else:
             R.skip(post_stage)
     except BaseException:

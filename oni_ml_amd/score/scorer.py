@@ -330,6 +330,38 @@ def tail_pairs(model, doc: torch.Tensor, word: torch.Tensor):
     return H.tail_mass(theta, phi, d32, w32), "pairs"
 
 
+def peer_topn(model, query: torch.Tensor, n: int):
+    """``((rows int32 [Q, n], dist float64 [Q, n], count int32 [Q]), path)``: the ``n`` θ rows nearest to every
+    ``query`` row in L1 distance over the whole row (all members), ascending by (distance, row), the query's own
+    row left out (``ops.hip.peer_topn`` on the GPU, its torch twin elsewhere: the same bits).  ``path``: the
+    kernel's form (``ops.hip.peer_theta_path``) or ``"cpu"``; ``model``: a TopicModel or an EnsembleModel."""
+    theta = model_tables3(model)[0].contiguous()
+    q32 = query.to(torch.int32).contiguous()
+    if theta.device.type == "cuda":
+        from ..ops import hip as H
+        return H.peer_topn(theta, q32, n), H.peer_theta_path(int(theta.shape[1]), int(theta.shape[2]))
+    from ..ops.reference import peer_topn as ref
+    return ref(theta, q32, n), "cpu"
+
+
+def peer_scores(model, rows: torch.Tensor, count: torch.Tensor, doc: torch.Tensor, word: torch.Tensor) -> torch.Tensor:
+    """float64 [n]: the mean score of every side's word at its document's peers.  ``rows`` [n, N] / ``count`` [n]:
+    the side's document's peers (``peer_topn``, gathered to the sides); ``doc`` / ``word``: the side's θ / φ row or
+    -1.  From 0.0, for i = 0 .. count - 1 in peer order, ``+ score(peer i, word)`` -- N calls of the scorers on
+    (peer i, word), a slot past the count masked -- then one division by (double)count.  NaN for a side without a
+    document, a φ row or a peer.  The scorers' own kernels or twins: the same bits on both devices."""
+    n, N = int(rows.shape[0]), int(rows.shape[1])
+    ok = (doc.reshape(-1) >= 0) & (word.reshape(-1) >= 0)
+    count = count.reshape(-1).to(torch.int64)
+    w = word.reshape(-1)
+    acc = torch.zeros(n, dtype=torch.float64, device=rows.device)
+    for i in range(N):
+        live = ok & (count > i)      # (a masked slot scores the default vector, which the select drops)
+        s = score(model, torch.where(live, rows[:, i].to(w.dtype), torch.full_like(w, -1)), w)[0]
+        acc = torch.where(live, acc + s, acc)
+    return torch.where(ok & (count > 0), acc / count.to(torch.float64), torch.full_like(acc, float("nan")))
+
+
 def rank_hosts(min_score: torch.Tensor, flagged: torch.Tensor, limit: Optional[int] = None) -> np.ndarray:
     """Document rows with at least one flagged side, ascending by their lowest score, ties to the lowest row
     (int64 host array); ``limit``: only the first ``limit`` of them (the MAXRESULTS radix select and its tie
