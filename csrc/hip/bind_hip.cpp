@@ -249,6 +249,29 @@ PYBIND11_MODULE(_onihip, m) {
     oni::launch_peer_topn(a, max_blocks, S(stream));
   });
 
+  m.def("topic_report_max", []() { return oni::kTopicReportMax; });
+  m.def("topic_columns_max", []() { return oni::kTopicColumnsMax; });
+  m.def("topic_threads", [](int N) { return oni::topic_threads(N); });
+  m.def("topic_merge_groups", [](int64_t nblk) { return oni::topic_merge_groups(nblk); });
+  m.def("topic_groups", [](int N, int wb) { return oni::topic_groups(N, wb); });
+  m.def("column_topn", [](u table, int64_t rows, int W, int64_t ld, u tau, int c0, int wb, int N, int64_t block,
+                          int64_t nblk, u scratch, u scratch2, u out_rows, u out_vals, u out_count, int max_blocks,
+                          u stream) {
+    oni::TopnArgs a{P<const double>(table), rows, W, ld, P<const double>(tau), c0, wb, N, block, nblk, P<double>(scratch), P<double>(scratch2),
+                    P<int>(out_rows), P<double>(out_vals), P<int>(out_count)};
+    oni::launch_column_topn(a, max_blocks, S(stream));
+  });
+  m.def("row_dominant", [](u table, int64_t rows, int R, int K, u arg, u counts, int max_blocks, u stream) {
+    oni::DominantArgs a{P<const double>(table), rows, R, K, P<int>(arg), P<unsigned long long>(counts)};
+    oni::launch_row_dominant(a, max_blocks, S(stream));
+  });
+  m.def("topic_sides", [](u theta, u phi, int R, int K, u doc, u word, int64_t n, u col, u resp, u host_share,
+                          u host_topic, int max_blocks, u stream) {
+    oni::TopicSidesArgs a{P<const double>(theta), P<const double>(phi), R, K, P<const int>(doc), P<const int>(word), n,
+                          P<int>(col), P<double>(resp), P<double>(host_share), P<int>(host_topic)};
+    oni::launch_topic_sides(a, max_blocks, S(stream));
+  });
+
   m.def("holdout_draw", [](u base, u counts, u chunk_off, int64_t nnz, int64_t chunks, unsigned long long key,
                            unsigned long long thr, int lane_tokens, u t, int max_blocks, u stream) {
     oni::HoldoutDrawArgs a{P<const int64_t>(base), P<const int64_t>(counts), P<const int64_t>(chunk_off), nnz, chunks,

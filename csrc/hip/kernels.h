@@ -427,6 +427,68 @@ struct PeerArgs {
 void launch_peer_topn(const PeerArgs& a, int max_blocks, hipStream_t s);
 int peer_theta_path(int R, int K);   // the PeerPath the launch takes at this row shape
 
+// --topic-report (topic_report.hip).  column_topn: per column j of table [rows][W] the N rows first in the total
+// order (value descending under IEEE >, row ascending) -- equal values, -0.0 and +0.0 among them, go to the lower
+// row, a NaN never enters: out_rows[j][0 .. out_count[j]) and out_vals[j][..]; the slots past the count hold -1 and
+// -inf.  The top N of a set under a total order does not depend on how the set is cut: the same bits for every
+// grid, block and batch, no atomics.  One launch handles the columns c0 .. c0 + wb - 1.
+constexpr int kTopicReportMax = 32;       // largest N
+constexpr int64_t kTopicRowsMax = ((int64_t)1 << 31) - 65536;   // largest table of column_topn
+constexpr int kTopicMergeGroup = 64;      // blocks whose lists one workgroup of pass 2 merges
+constexpr int kTopicColumnsMax = 8192;    // largest R K of row_dominant (its LDS histogram: 32 KiB)
+struct TopnArgs {
+  const double* table;   // [rows][ld], the first W of a row its values
+  int64_t rows;          // 1 <= rows <= kTopicRowsMax
+  int W;                 // doubles of a row, >= 1
+  int64_t ld;            // doubles from a row to the next, >= W (a strided sample of a table: a multiple of W)
+  const double* tau;     // [W] or null: pass 1 skips a value below tau[column] -- a lower bound of the column's
+                         // N-th value (that of a subset of the rows), so nothing listed is skipped
+  int c0, wb;            // the launch's columns: 0 <= c0, 1 <= wb, c0 + wb <= W
+  int N;                 // 1 <= N <= kTopicReportMax
+  int64_t block;         // rows of a block, >= 1
+  int64_t nblk;          // ceil(rows / block)
+  double* scratch;       // nblk * N * wb * 12 bytes: [nblk][N][wb] doubles (value), then [nblk][N][wb] ints (row)
+  double* scratch2;      // nblk > kTopicMergeGroup: the same layout for topic_merge_groups(nblk) blocks; else unused
+  int* out_rows;         // [W][N]
+  double* out_vals;      // [W][N]
+  int* out_count;        // [W]
+};
+// max_blocks: cap on the workgroups per launch (0: 65536)
+void launch_column_topn(const TopnArgs& a, int max_blocks, hipStream_t s);
+int topic_merge_groups(int64_t nblk);   // lists of the second scratch (0: pass 2 has one level)
+int topic_threads(int N);           // lanes of a workgroup at this N (the lists are N x lanes x 12 bytes of LDS)
+int topic_groups(int N, int wb);    // row sub-groups of a workgroup at this N and column count (1: a lane per column)
+
+// row_dominant: arg[row][r] = the first k attaining the maximum of table[row][r][0 .. K) (a NaN never wins; -1: all
+// NaN); counts[r][k] += the rows whose arg is k (integer atomics; the caller zeroes counts).
+struct DominantArgs {
+  const double* table;          // [rows][R][K]
+  int64_t rows;                 // rows R < 2^31
+  int R, K;                     // R K <= kTopicColumnsMax
+  int* arg;                     // [rows][R]
+  unsigned long long* counts;   // [R][K]
+};
+void launch_row_dominant(const DominantArgs& a, int max_blocks, hipStream_t s);
+
+// topic_sides: per side (doc, word), over j = 0 .. R K - 1 in order p_j = theta[doc][j] * phi[word][j] (one rounded
+// product): col = the first j with the greatest p_j (a NaN never wins), resp = p* / (s * (double)R) with s the
+// side's score as score_ensemble.hip computes it, host_share = theta[doc][col], host_topic = the first k attaining
+// the maximum of theta[doc][col / K][.].  A side with doc < 0, word < 0 or NaN products only: -1, NaN, NaN, -1 --
+// so the scorers' default vector of a miss never enters, and the launch takes no default value.
+struct TopicSidesArgs {
+  const double* theta;   // [D][R][K]
+  const double* phi;     // [V][R][K]
+  int R, K;
+  const int* doc;        // [n] theta rows or -1 (bounds checked on the host)
+  const int* word;       // [n] phi rows or -1
+  int64_t n;             // 0 <= n < 2^31
+  int* col;              // [n]
+  double* resp;          // [n]
+  double* host_share;    // [n]
+  int* host_topic;       // [n]
+};
+void launch_topic_sides(const TopicSidesArgs& a, int max_blocks, hipStream_t s);
+
 // --holdout (holdout.hip).  holdout_draw: t[e] = the tokens j of CSR entry e, 0 <= j < counts[e], with
 // splitmix64(key ^ (base[e] + j)) >> 11 < thr -- integers only, so t depends on nothing but (key, thr, corpus).
 // An entry of at most lane_tokens tokens is drawn by one lane; a longer one is cut into chunks of

@@ -94,12 +94,14 @@ def clean_workdir(lpath: str):
     """ml_ops.sh:53-54: remove stale *.dat,*.beta,*.gamma,*.other,*.pkl; keep *.csv (analyst feedback) -- except
     what an earlier --explain, --expect or --tail run left, ``<type>_explain.csv``, ``word_fields.npz``,
     ``<type>_expect.csv`` and ``<type>_tail.csv``, and an earlier --peers run's ``<type>_peers.csv`` and
-    ``<type>_peer_groups.csv``: a fresh run removes them with or without the flags, since their
+    ``<type>_peer_groups.csv``, and an earlier --topic-report run's ``<type>_topics.csv``, ``<type>_topic_words.csv``,
+    ``<type>_topic_hosts.csv`` and ``<type>_topic.csv``: a fresh run removes them with or without the flags, since their
     lines would not describe this run's results file.  ``ensemble/`` and ``holdout/`` (an earlier run's members, its
     held-out records and training fits) go too."""
     for pat in ("*.dat", "*.beta", "*.gamma", "*.other", "*.pkl", "checkpoint.npz", "final_model.npz",
                 "final_gamma.rank*.npz", "word_fields.npz", "*_explain.csv", "*_expect.csv",
-                "*_tail.csv", "*_peers.csv", "*_peer_groups.csv"):
+                "*_tail.csv", "*_peers.csv", "*_peer_groups.csv", "*_topics.csv", "*_topic_words.csv",
+                "*_topic_hosts.csv", "*_topic.csv"):
         for f in glob.glob(os.path.join(lpath, pat)):
             os.unlink(f)
     shutil.rmtree(os.path.join(lpath, ".stages"), ignore_errors=True)
@@ -142,6 +144,12 @@ def cmd_ml_ops(argv):
                          "the N hosts nearest to its host in topic space (L1 distance of the theta rows), and "
                          "peer_lift, that mean score over the host's own: far above 1, the host's peers do this "
                          "routinely and the host does not (1 <= N <= 16; 0 or PEERS unset: off; one process only)")
+    ap.add_argument("--topic-report", type=int, default=None, metavar="N",
+                    help="also describe the model: <type>_topics.csv (every topic's share of the day, the hosts and "
+                         "words it dominates), <type>_topic_words.csv and <type>_topic_hosts.csv (the N words and hosts "
+                         "that carry it) and <type>_topic.csv, line for line with the results file: the topic that "
+                         "explains every written side and its share of the side's score (1 <= N <= 32; 0 or "
+                         "TOPIC_REPORT unset: off; one process only)")
     ap.add_argument("--holdout", type=float, default=None, metavar="F",
                     help="hold the fraction F (0 < F <= 0.5) of every document's tokens out, fit on the rest and write "
                          "the held-out perplexity per topic count to <LPATH>/holdout/ (or HOLDOUT; one process only)")
@@ -201,7 +209,8 @@ def cmd_ml_ops(argv):
                            write_doc_wc=a.keep_doc_wc, word_assignments=a.word_assignments,
                            rank_gamma=a.rank_gamma, verbose=not a.quiet, cuts=a.cuts, hdfs=a.hdfs or None,
                            hadoop=a.hadoop, host_report=a.host_report, ensemble=a.ensemble, explain=a.explain,
-                           expect=a.expect, tail=a.tail, tail_tol=a.tail_tol, peers=a.peers, holdout=a.holdout,
+                           expect=a.expect, tail=a.tail, tail_tol=a.tail_tol, peers=a.peers,
+                           topic_report=a.topic_report, holdout=a.holdout,
                            holdout_topics=a.holdout_topics, holdout_select=a.holdout_select)
     # --ensemble / ENSEMBLE (the site file and the environment set it too): refused here, before anything is
     # written and before a process group is asked for
@@ -220,6 +229,8 @@ def cmd_ml_ops(argv):
         raise ValueError(CFG.TAIL_ONE_PROCESS)
     # --peers / PEERS likewise
     CFG.RunConfig.check_peers(first.peers, a.gpus, a.hdfs, int(os.environ.get("WORLD_SIZE", "1")))
+    # --topic-report / TOPIC_REPORT likewise
+    CFG.RunConfig.check_topic_report(first.topic_report, a.gpus, a.hdfs, int(os.environ.get("WORLD_SIZE", "1")))
     # --holdout / HOLDOUT likewise
     CFG.RunConfig.check_holdout(first.holdout, first.holdout_list(), first.holdout_select, a.start, a.compat, a.dsource,
                                 a.backend, a.gpus, a.hdfs, int(os.environ.get("WORLD_SIZE", "1")))

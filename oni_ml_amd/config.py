@@ -27,7 +27,8 @@ from .models.lda.settings import LDASettings
 
 ENV_KEYS = ("FLOW_PATH", "DNS_PATH", "PROXY_PATH", "HPATH", "LPATH", "LUSER", "TOL", "DUPFACTOR", "KRB_AUTH", "NODES",
             "UINODE", "RPATH", "LDAPATH", "SPK_EXEC", "SPK_EXEC_MEM", "TOP1M", "CUT", "MAXRESULTS", "ENSEMBLE", "EXPLAIN",
-            "HOLDOUT", "HOLDOUT_TOPICS", "TAIL", "TAIL_TOL", "EXPECT", "PEERS")
+            "HOLDOUT", "HOLDOUT_TOPICS", "TAIL", "TAIL_TOL", "EXPECT", "PEERS",
+            "TOPIC_REPORT")
 
 # proxy has no multi-rank, sharded or HDFS-staged form
 PROXY_ONE_PROCESS = "proxy runs on one process: launch it without torchrun, with --gpus 1 and without --hdfs"
@@ -74,6 +75,20 @@ PEERS_MAX = 16             # largest N of --peers (csrc/hip/kernels.h kPeersMax)
 # MI355X: profiles/peers.md)
 PEERS_BLOCK = 4096
 PEERS_SCRATCH_MB = 256
+
+# the topic report is made from one process's written sides and its whole theta and phi tables: no multi-rank,
+# sharded or HDFS-staged form
+TOPIC_REPORT_ONE_PROCESS = ("--topic-report runs on one process: launch it without torchrun, with --gpus 1 and "
+                            "without --hdfs")
+TOPIC_REPORT_MAX = 32      # largest N of --topic-report (csrc/hip/kernels.h kTopicReportMax)
+# rows of one block of ops.hip.column_topn and the cap on its per-block lists (N x 12 bytes per column and block; more
+# columns: batches).  Neither changes a bit of the result: the values move time only (measured on an MI355X:
+# profiles/topic_report.md)
+TOPIC_BLOCK = 4096
+TOPIC_SCRATCH_MB = 256
+# rows of the strided sample whose N-th value per column lets the pass over all rows skip what lies below it (a
+# table of fewer than twice as many rows is not sampled).  No bit of the result depends on it either
+TOPIC_SAMPLE = 8192
 
 # --holdout: the split and the K fits are one process's: no multi-rank, sharded or HDFS-staged form
 HOLDOUT_ONE_PROCESS = "--holdout runs on one process: launch it without torchrun, with --gpus 1 and without --hdfs"
@@ -153,6 +168,10 @@ class RunConfig:
     peers: int = 0                        # --peers / PEERS: also write <type>_peers.csv and <type>_peer_groups.csv,
                                           # every written side scored at its host's N nearest hosts in topic space
                                           # (1 <= N <= PEERS_MAX); 0: off
+    topic_report: int = 0                 # --topic-report / TOPIC_REPORT: also write <type>_topics.csv,
+                                          # <type>_topic_words.csv, <type>_topic_hosts.csv (the N words and hosts that
+                                          # carry every topic) and <type>_topic.csv (the topic that explains every
+                                          # written side); 1 <= N <= TOPIC_REPORT_MAX; 0: off
     holdout: float = 0.0                  # --holdout / HOLDOUT: hold this fraction of every document's tokens out, fit
                                           # on the rest and report the held-out perplexity per topic count; 0: off
     holdout_topics: str = ""              # --holdout-topics / HOLDOUT_TOPICS: "K1,K2,..." to evaluate; "": topics alone
@@ -241,6 +260,7 @@ class RunConfig:
         if self.tail and (self.gpus > 1 or self.hdfs):
             raise ValueError(TAIL_ONE_PROCESS)
         self.peers = self.check_peers(self.peers, self.gpus, self.hdfs)
+        self.topic_report = self.check_topic_report(self.topic_report, self.gpus, self.hdfs)
         self.check_ensemble(self.ensemble, self.start, self.gpus, self.hdfs)
         self.check_holdout(self.holdout, self.holdout_list(), self.holdout_select, self.start, self.compat,
                            self.dsource, self.backend, self.gpus, self.hdfs)
@@ -268,6 +288,18 @@ class RunConfig:
             raise ValueError(f"--peers must be 0 (off) or in [1, {PEERS_MAX}], got {n}")
         if gpus > 1 or hdfs or world > 1:
             raise ValueError(PEERS_ONE_PROCESS)
+        return n
+
+    @staticmethod
+    def check_topic_report(n, gpus: int = 1, hdfs: bool = False, world: int = 1) -> int:
+        """The --topic-report rules, also applied by the command line before anything is written."""
+        n = int(n)
+        if n == 0:
+            return 0
+        if not 1 <= n <= TOPIC_REPORT_MAX:
+            raise ValueError(f"--topic-report must be 0 (off) or in [1, {TOPIC_REPORT_MAX}], got {n}")
+        if gpus > 1 or hdfs or world > 1:
+            raise ValueError(TOPIC_REPORT_ONE_PROCESS)
         return n
 
     @staticmethod
@@ -380,6 +412,8 @@ def _apply(cfg: RunConfig, layer: Dict[str, object]):
         cfg.tail_tol = float(layer["TAIL_TOL"])
     if "PEERS" in layer and layer["PEERS"] not in ("", None):
         cfg.peers = int(layer["PEERS"])
+    if "TOPIC_REPORT" in layer and layer["TOPIC_REPORT"] not in ("", None):
+        cfg.topic_report = int(layer["TOPIC_REPORT"])
     if "HOLDOUT" in layer and layer["HOLDOUT"] not in ("", None):
         cfg.holdout = float(layer["HOLDOUT"])
     if "HOLDOUT_TOPICS" in layer and layer["HOLDOUT_TOPICS"] not in ("", None):

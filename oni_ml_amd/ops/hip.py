@@ -909,6 +909,171 @@ def peer_topn(theta3, query, n, block=None, max_blocks: int = 0, scratch_mb=None
     return rows, dist, count
 
 
+def topic_path(n: int, W: int) -> str:
+    """Which form of the column top-N kernel ``W`` columns take at ``n`` (csrc/hip/topic_report.hip):
+    ``columns`` -- a lane per column -- or ``subgroups<G>`` -- the workgroup's lanes in G row sub-groups of W lanes,
+    where the table is narrower than half a workgroup."""
+    G = lib().topic_groups(int(n), int(W))
+    return "columns" if G == 1 else f"subgroups{G}"
+
+
+def column_topn(table, n, block=None, max_blocks: int = 0, scratch_mb=None, sample=None):
+    """Per column of ``table`` the ``n`` rows with the greatest values (csrc/hip/topic_report.hip;
+    ``ops.reference.column_topn`` is the twin): ``(rows int32 [W, n], vals float64 [W, n], count int32 [W])`` as new
+    device tensors.
+
+    ``table`` [rows, W] float64.  Listed are the rows first in the total order (value descending under IEEE ``>``,
+    row ascending): equal values, -0.0 and +0.0 among them, go to the lower row, a NaN never; ``count`` of them, the
+    slots past it -1 and -inf.  The same bits for every grid, ``block`` (``config.TOPIC_BLOCK`` rows) and batch; no
+    atomics.
+
+    The per-block lists (n x 12 bytes per column and block) live in a scratch of at most ``scratch_mb`` MiB
+    (``config.TOPIC_SCRATCH_MB``): more columns than fit are processed in batches.  Everything is checked on the
+    host before the launch; an empty table launches nothing.  ``max_blocks``: cap on the workgroups per launch
+    (tests: a small cap makes the grid-stride loops wrap).
+
+    A table of at least 2 x ``sample`` rows (``config.TOPIC_SAMPLE``) is read twice: first the same kernels list
+    every (rows // sample)-th row; a column's n-th value there is a lower bound of its n-th value in the table, so
+    the pass over all rows skips what lies below it -- after that almost nothing reaches a list and the pass is a
+    compare per load.  A bound from a subset of the rows excludes nothing that is listed: the same bits."""
+    import operator
+    _max_blocks(max_blocks)
+    TB = operator.index(_CFG.TOPIC_BLOCK if block is None else block)
+    if TB < 1 or TB >= 1 << 31:
+        raise ValueError(f"column_topn: block must be in [1, 2^31), got {TB}")
+    S = operator.index(_CFG.TOPIC_SAMPLE if sample is None else sample)
+    if S < 1:
+        raise ValueError(f"column_topn: sample must be >= 1, got {S}")
+    cap_mb = float(_CFG.TOPIC_SCRATCH_MB if scratch_mb is None else scratch_mb)
+    if not cap_mb > 0:
+        raise ValueError(f"column_topn: scratch_mb must be > 0, got {scratch_mb!r}")
+    N = operator.index(n)
+    if not 1 <= N <= _CFG.TOPIC_REPORT_MAX:
+        raise ValueError(f"column_topn: n must be in [1, {_CFG.TOPIC_REPORT_MAX}], got {N}")
+    if not isinstance(table, torch.Tensor) or table.dim() != 2:
+        raise ValueError("table: expected a [rows, W] tensor")
+    if table.dtype != torch.float64:
+        raise ValueError(f"table: expected torch.float64, got {table.dtype}")
+    if not table.is_cuda:
+        raise ValueError("table: must be a GPU tensor")
+    if not table.is_contiguous():
+        raise ValueError("table: must be contiguous")
+    dev = table.device
+    D, W = (int(x) for x in table.shape)
+    if D > (1 << 31) - 65536 or W >= 1 << 31:
+        raise ValueError(f"column_topn: table {D} x {W} (rows <= 2^31 - 65536, W < 2^31)")
+    rows = torch.full((W, N), -1, dtype=torch.int32, device=dev)
+    vals = torch.full((W, N), float("-inf"), dtype=torch.float64, device=dev)
+    count = torch.zeros(W, dtype=torch.int32, device=dev)
+    if D == 0 or W == 0:
+        return rows, vals, count
+    L = lib()
+    if L.topic_report_max() != _CFG.TOPIC_REPORT_MAX:
+        raise RuntimeError("column_topn: config.TOPIC_REPORT_MAX differs from the compiled limit")
+    nblk = -(-D // TB)
+    # the sample: every stride-th row.  Its pass has no bound yet, so its time goes to list inserts, not to loads:
+    # blocks of at most 256 rows spread the S rows over 32 workgroups or more (a 4096-row block: two)
+    stride = D // S if D >= 2 * S else 0
+    s_rows_n = (D - 1) // stride + 1 if stride else 0
+    s_block = min(TB, 256)
+    s_nblk = -(-s_rows_n // s_block)
+    per_col = 12 * N * max(nblk, s_nblk)
+    batch = max(1, min(W, int(cap_mb * (1 << 20)) // per_col))
+    T = L.topic_threads(N)
+    if batch < W and batch >= T:
+        batch -= batch % T      # whole tiles of columns
+    # doubles first, then ints: [nblk][N][batch] of each, rounded up to whole doubles
+    cells = batch * max(nblk, s_nblk) * N
+    scratch = torch.empty(cells + (cells + 1) // 2, dtype=torch.float64, device=dev)
+    # pass 2 in two levels where the blocks are many: the lists of the groups of blocks
+    cells2 = batch * max(L.topic_merge_groups(nblk), L.topic_merge_groups(s_nblk)) * N
+    scratch2 = torch.empty(cells2 + (cells2 + 1) // 2, dtype=torch.float64, device=dev) if cells2 else None
+    p2 = scratch2.data_ptr() if cells2 else 0
+    if stride:
+        s_out = (torch.empty((W, N), dtype=torch.int32, device=dev),
+                 torch.empty((W, N), dtype=torch.float64, device=dev), torch.empty(W, dtype=torch.int32, device=dev))
+    for c0 in range(0, W, batch):
+        wb = int(min(batch, W - c0))
+        tau = 0
+        if stride:
+            # the sample's N-th value per column (-inf where it lists fewer): a lower bound of the table's
+            L.column_topn(table.data_ptr(), s_rows_n, W, stride * W, 0, int(c0), wb, N, int(s_block), int(s_nblk),
+                          scratch.data_ptr(), p2, s_out[0].data_ptr(), s_out[1].data_ptr(), s_out[2].data_ptr(),
+                          int(max_blocks), _stream())
+            bound = s_out[1][:, N - 1].contiguous()
+            tau = bound.data_ptr()
+        L.column_topn(table.data_ptr(), D, W, W, tau, int(c0), wb, N, int(TB), int(nblk), scratch.data_ptr(), p2,
+                      rows.data_ptr(), vals.data_ptr(), count.data_ptr(), int(max_blocks), _stream())
+    return rows, vals, count
+
+
+def row_dominant(table3, max_blocks: int = 0):
+    """The dominant topic of every (row, member) and the rows per (member, topic) (csrc/hip/topic_report.hip;
+    ``ops.reference.row_dominant`` is the twin): ``(arg int32 [rows, R], counts int64 [R, K])`` as new device
+    tensors.  ``table3`` [rows, R, K] float64; ``arg`` the first k attaining the maximum of ``table3[row, r, :]``, a
+    NaN never, -1 when every entry is NaN.  The counts are integers, added with integer atomics from per-workgroup
+    LDS histograms.  Everything is checked on the host before the launch; no row launches nothing."""
+    _max_blocks(max_blocks)
+    if not isinstance(table3, torch.Tensor) or table3.dim() != 3:
+        raise ValueError("table: expected a [rows, R, K] tensor")
+    n, R, K = (int(x) for x in table3.shape)
+    L = lib()
+    if R < 1 or K < 1 or R * K > L.topic_columns_max():
+        raise ValueError(f"row_dominant: R and K must be >= 1 and R K <= {L.topic_columns_max()}, got {R} x {K}")
+    _table3("table", table3, R, K)
+    if n * R >= 1 << 31:
+        raise ValueError(f"row_dominant: {n} rows x {R} members (rows R < 2^31)")
+    dev = table3.device
+    arg = torch.empty((n, R), dtype=torch.int32, device=dev)
+    counts = torch.zeros((R, K), dtype=torch.int64, device=dev)
+    if n:
+        L.row_dominant(table3.data_ptr(), n, R, K, arg.data_ptr(), counts.data_ptr(), int(max_blocks), _stream())
+    return arg, counts
+
+
+def topic_sides(theta3, phi3, doc, word, max_blocks: int = 0):
+    """The topic that explains every side (csrc/hip/topic_report.hip; ``ops.reference.topic_sides`` is the twin):
+    ``(col int32 [n], resp float64 [n], host_share float64 [n], host_topic int32 [n])`` as new device tensors.
+
+    ``theta3`` [D, R, K] / ``phi3`` [V, R, K] float64; ``doc`` / ``word`` int32 [n]: the side's rows or -1.  Over the
+    columns j = r K + k in order ``p_j = theta[d, j] * phi[w, j]``, one rounded product; ``col`` the first j with
+    the greatest p_j, a NaN never; ``resp = p* / (s * R)`` with s the side's score as ``score_ensemble`` computes
+    it; ``host_share = theta[d, col]``; ``host_topic`` the first k attaining the maximum of the host's row in col's
+    member.  A side without a θ row or a φ row, or with NaN products only: -1, NaN, NaN, -1.  Every index is checked
+    on the host before the launch; no side launches nothing."""
+    _max_blocks(max_blocks)
+    if not isinstance(theta3, torch.Tensor) or theta3.dim() != 3:
+        raise ValueError("theta: expected a [rows, R, K] tensor")
+    D, R, K = (int(x) for x in theta3.shape)
+    if R < 1 or K < 1 or R * K >= 1 << 31:
+        raise ValueError(f"topic_sides: R and K must be >= 1 and R K < 2^31, got {R} x {K}")
+    _table3("theta", theta3, R, K)
+    dev = theta3.device
+    _table3("phi", phi3, R, K, dev)
+    V = int(phi3.shape[0])
+    if not isinstance(doc, torch.Tensor) or doc.dim() != 1:
+        raise ValueError("doc: expected a 1-D tensor")
+    n = doc.numel()
+    if n >= 1 << 31:
+        raise ValueError(f"topic_sides: {n} sides (n < 2^31)")
+    _index("doc", doc, torch.int32, (n,), dev)
+    _index("word", word, torch.int32, (n,), dev)
+    col = torch.empty(n, dtype=torch.int32, device=dev)
+    resp = torch.empty(n, dtype=torch.float64, device=dev)
+    share = torch.empty(n, dtype=torch.float64, device=dev)
+    ht = torch.empty(n, dtype=torch.int32, device=dev)
+    if n == 0:
+        return col, resp, share, ht
+    # index bounds (host check before a gather kernel touches memory)
+    if int(doc.max()) >= D or int(doc.min()) < -1:
+        raise ValueError("doc: index out of range")
+    if int(word.max()) >= V or int(word.min()) < -1:
+        raise ValueError("word: index out of range")
+    lib().topic_sides(theta3.data_ptr(), phi3.data_ptr(), R, K, doc.data_ptr(), word.data_ptr(), n, col.data_ptr(),
+                      resp.data_ptr(), share.data_ptr(), ht.data_ptr(), int(max_blocks), _stream())
+    return col, resp, share, ht
+
+
 def holdout_draw(doc_ptr, counts, seed, thr, max_blocks: int = 0, rules: bool = True, lane_tokens=None):
     """Held-out tokens of every CSR entry (csrc/hip/holdout.hip; ``ops.reference.holdout_draw`` is the twin): int64
     [nnz] as a new device tensor.

@@ -443,6 +443,133 @@ def peer_topn(theta3, query, n, slab: int = PEERS_SLAB):
     return rows, dist, count
 
 
+TOPIC_SLAB = 1 << 22      # doubles the topic report's twins hold at a time
+
+
+def column_topn(table, n, slab: int = TOPIC_SLAB):
+    """Torch twin of ``ops.hip.column_topn`` (csrc/hip/topic_report.hip) on any device, bit for bit, and the CPU
+    pipeline's path: ``(rows int32 [W, n], vals float64 [W, n], count int32 [W])``.  Per column of ``table``
+    [rows, W] float64 the ``n`` rows first in the total order (value descending under IEEE ``>``, row ascending):
+    equal values, -0.0 and +0.0 among them, go to the lower row; a NaN is never listed; ``count`` is the number
+    listed, the slots past it hold -1 and -inf.  The rows are taken in slabs of at most ``slab`` / W: a stable
+    ascending sort of ``0.0 - value`` (both zeros become +0.0, equal keys stay in row order, torch puts NaN last),
+    the slab's first ``n`` merged with the list so far, whose rows are all lower, by the same sort."""
+    from ..config import TOPIC_REPORT_MAX
+    n = int(n)
+    if not 1 <= n <= TOPIC_REPORT_MAX:
+        raise ValueError(f"column_topn: n must be in [1, {TOPIC_REPORT_MAX}], got {n}")
+    if table.dim() != 2 or table.dtype != torch.float64:
+        raise ValueError("column_topn: table [rows, W] float64")
+    rows_n, W = (int(x) for x in table.shape)
+    dev = table.device
+    nan = float("nan")
+    vals = torch.full((W, n), nan, dtype=torch.float64, device=dev)      # NaN: an empty slot, it sorts last
+    rows = torch.full((W, n), -1, dtype=torch.int64, device=dev)
+    step = max(1, int(slab) // max(W, 1))
+    for r0 in range(0, rows_n if W else 0, step):
+        x = table[r0:r0 + step].t()                                      # [W, m], a column's rows ascending
+        m = min(n, int(x.shape[1]))
+        order = torch.sort(0.0 - x, dim=1, stable=True)[1][:, :m]
+        cand_v = torch.cat([vals, torch.gather(x, 1, order)], 1)         # the list's rows are below the slab's
+        cand_r = torch.cat([rows, order + r0], 1)
+        keep = torch.sort(0.0 - cand_v, dim=1, stable=True)[1][:, :n]
+        vals, rows = torch.gather(cand_v, 1, keep), torch.gather(cand_r, 1, keep)
+    live = vals == vals
+    return (torch.where(live, rows, torch.full_like(rows, -1)).to(torch.int32),
+            torch.where(live, vals, torch.full_like(vals, float("-inf"))), live.sum(1).to(torch.int32))
+
+
+def row_dominant(table3, slab: int = TOPIC_SLAB):
+    """Torch twin of ``ops.hip.row_dominant`` (csrc/hip/topic_report.hip) on any device:
+    ``(arg int32 [rows, R], counts int64 [R, K])``.  ``arg``: the first k attaining the maximum of
+    ``table3[row, r, :]`` ([rows, R, K] float64; a NaN never wins, -1 when every entry is NaN); ``counts``: the rows
+    per (r, k).  Rows in slabs of at most ``slab`` / (R K): integers, no slab shows."""
+    if table3.dim() != 3 or table3.dtype != torch.float64:
+        raise ValueError("row_dominant: table [rows, R, K] float64")
+    n, R, K = (int(x) for x in table3.shape)
+    dev = table3.device
+    arg = torch.full((n, R), -1, dtype=torch.int32, device=dev)
+    counts = torch.zeros(R * K, dtype=torch.int64, device=dev)
+    step = max(1, int(slab) // max(R * K, 1))
+    base = (torch.arange(R, device=dev, dtype=torch.int64) * K).unsqueeze(0)
+    for r0 in range(0, n if R * K else 0, step):
+        t = table3[r0:r0 + step]
+        best = torch.full(t.shape[:2], -1, dtype=torch.int64, device=dev)
+        bv = torch.zeros(t.shape[:2], dtype=torch.float64, device=dev)
+        for k in range(K):
+            v = t[:, :, k]
+            take = (v == v) & ((best < 0) | (v > bv))
+            best = torch.where(take, torch.full_like(best, k), best)
+            bv = torch.where(take, v, bv)
+        arg[r0:r0 + step] = best.to(torch.int32)
+        hit = best >= 0
+        counts.index_add_(0, (best + base)[hit], torch.ones(int(hit.sum()), dtype=torch.int64, device=dev))
+    return arg, counts.reshape(R, K)
+
+
+def topic_sides(theta3, phi3, doc, word, slab: int = TOPIC_SLAB):
+    """Torch twin of ``ops.hip.topic_sides`` (csrc/hip/topic_report.hip) on any device, bit for bit:
+    ``(col int32 [n], resp float64 [n], host_share float64 [n], host_topic int32 [n])``.  ``theta3`` [D, R, K] /
+    ``phi3`` [V, R, K]; ``doc`` / ``word``: the side's rows or -1.  Over the columns j = r K + k in order
+    ``p_j = theta[d, j] * phi[w, j]``, one rounded product; ``col`` the first j with the greatest p_j (a NaN never
+    wins); ``resp = p* / (s * R)`` with s the side's score as ``score_ensemble`` adds it (member sums in topic order
+    from 0.0, the members in member order from 0.0, one division by R) -- one rounded multiply, exact at R = 1, and
+    one rounded division; ``host_share = theta[d, col]``; ``host_topic`` the first k attaining the maximum of
+    ``theta[d, col // K, :]``.  A side without a θ row or a φ row, or with NaN products only: -1, NaN, NaN, -1 (the
+    default vector of a miss takes no part).  Sides in slabs of at most ``slab`` / (R K)."""
+    if theta3.dim() != 3 or phi3.dim() != 3 or theta3.dtype != torch.float64 or phi3.dtype != torch.float64 or \
+            tuple(theta3.shape[1:]) != tuple(phi3.shape[1:]):
+        raise ValueError("topic_sides: theta [D, R, K] and phi [V, R, K] float64")
+    D, R, K = (int(x) for x in theta3.shape)
+    V = int(phi3.shape[0])
+    d_all, w_all = doc.reshape(-1).to(torch.int64), word.reshape(-1).to(torch.int64)
+    n = d_all.numel()
+    dev = theta3.device
+    if w_all.numel() != n:
+        raise ValueError("topic_sides: doc and word differ in length")
+    if n and (int(d_all.max()) >= D or int(d_all.min()) < -1):
+        raise ValueError("doc: index out of range")
+    if n and (int(w_all.max()) >= V or int(w_all.min()) < -1):
+        raise ValueError("word: index out of range")
+    nan = float("nan")
+    col = torch.full((n,), -1, dtype=torch.int32, device=dev)
+    resp = torch.full((n,), nan, dtype=torch.float64, device=dev)
+    share = torch.full((n,), nan, dtype=torch.float64, device=dev)
+    ht = torch.full((n,), -1, dtype=torch.int32, device=dev)
+    if n == 0 or D == 0 or V == 0 or R * K == 0:
+        return col, resp, share, ht
+    step = max(1, int(slab) // (R * K))
+    for s0 in range(0, n, step):
+        d, w = d_all[s0:s0 + step], w_all[s0:s0 + step]
+        has = (d >= 0) & (w >= 0)
+        tr = theta3[d.clamp_min(0)]                                      # [m, R, K]
+        pr = phi3[w.clamp_min(0)]
+        m = int(d.numel())
+        best = torch.full((m,), -1, dtype=torch.int64, device=dev)
+        bp = torch.zeros(m, dtype=torch.float64, device=dev)
+        total = torch.zeros(m, dtype=torch.float64, device=dev)
+        for r in range(R):
+            s = torch.zeros(m, dtype=torch.float64, device=dev)
+            for k in range(K):
+                p = tr[:, r, k] * pr[:, r, k]                            # rounded product, then rounded sum
+                s = s + p
+                take = (p == p) & ((best < 0) | (p > bp))
+                best = torch.where(take, torch.full_like(best, r * K + k), best)
+                bp = torch.where(take, p, bp)
+            total = total + s
+        ok = has & (best >= 0)
+        j = best.clamp_min(0)
+        den = (total / float(R)) * float(R)
+        own = torch.gather(tr, 1, (j // K).reshape(m, 1, 1).expand(m, 1, K)).reshape(m, 1, K)
+        col[s0:s0 + step] = torch.where(ok, best, torch.full_like(best, -1)).to(torch.int32)
+        resp[s0:s0 + step] = torch.where(ok, bp / den, torch.full_like(bp, nan))
+        share[s0:s0 + step] = torch.where(ok, torch.gather(tr.reshape(m, R * K), 1, j.unsqueeze(1)).reshape(-1),
+                                          torch.full_like(bp, nan))
+        ht[s0:s0 + step] = torch.where(ok, row_dominant(own)[0].reshape(-1).to(torch.int64),
+                                       torch.full_like(best, -1)).to(torch.int32)
+    return col, resp, share, ht
+
+
 def select_lowest(key, flag, limit, with_count: bool = False):
     """Torch twin of ``ops.hip.select_lowest`` (csrc/hip/select_lowest.hip) on any device: the row indices
     (int64, ascending) of the ``limit`` flagged rows that a stable ascending sort of their keys puts first, all

@@ -181,6 +181,10 @@ def run_stages(cfg, spec: PipelineSpec, device=None, log=print) -> dict:
                                                  "peer_identical", "peer_lift_hist")}
                     summary.update(peers)
                     R.emit(dict(stage=post_stage + "_detail", **peers))
+                if cfg.topic_report:
+                    topics = {k: res[k] for k in C.TOPIC_REPORT_KEYS}
+                    summary.update(topics)
+                    R.emit(dict(stage=post_stage + "_detail", **topics))
         else:
             R.skip(post_stage)
     except BaseException:

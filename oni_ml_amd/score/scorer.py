@@ -362,6 +362,46 @@ def peer_scores(model, rows: torch.Tensor, count: torch.Tensor, doc: torch.Tenso
     return torch.where(ok & (count > 0), acc / count.to(torch.float64), torch.full_like(acc, float("nan")))
 
 
+def column_topn(table: torch.Tensor, n: int):
+    """``((rows int32 [W, n], vals float64 [W, n], count int32 [W]), path)``: per column of ``table`` [rows, W] the
+    ``n`` rows with the greatest values, descending, ties to the lower row, a NaN never (``ops.hip.column_topn`` on
+    the GPU, its torch twin elsewhere: the same bits).  ``path``: the kernel's form (``ops.hip.topic_path``) or
+    ``"cpu"``."""
+    table = table.contiguous()
+    if table.device.type == "cuda":
+        from ..ops import hip as H
+        return H.column_topn(table, n), H.topic_path(n, int(table.shape[1]))
+    from ..ops.reference import column_topn as ref
+    return ref(table, n), "cpu"
+
+
+def row_dominant(table3: torch.Tensor):
+    """``((arg int32 [rows, R], counts int64 [R, K]), path)``: the first topic attaining the maximum of every
+    (row, member) of ``table3`` [rows, R, K] and the rows per (member, topic) (``ops.hip.row_dominant`` on the GPU,
+    its torch twin elsewhere).  ``path``: ``"lanes"`` or ``"cpu"``."""
+    table3 = table3.contiguous()
+    if table3.device.type == "cuda":
+        from ..ops.hip import row_dominant as fn
+        return fn(table3), "lanes"
+    from ..ops.reference import row_dominant as ref
+    return ref(table3), "cpu"
+
+
+def topic_sides(model, doc: torch.Tensor, word: torch.Tensor):
+    """``((col int32 [n], resp float64 [n], host_share float64 [n], host_topic int32 [n]), path)`` of the sides: the
+    column j = member K + topic with the greatest θ φ product, its share ``resp`` of the side's score, the host's θ
+    there and the host's own dominant topic in that member (``ops.hip.topic_sides`` on the GPU, its torch twin
+    elsewhere: the same bits).  ``model``: a TopicModel or an EnsembleModel; ``doc`` / ``word``: θ / φ rows or -1;
+    ``path``: ``"lanes"`` or ``"cpu"``."""
+    theta, phi = model_tables3(model)
+    i32 = lambda t: t.to(torch.int32).contiguous()      # noqa: E731
+    if theta.device.type == "cuda":
+        from ..ops.hip import topic_sides as fn
+        return fn(theta.contiguous(), phi.contiguous(), i32(doc), i32(word)), "lanes"
+    from ..ops.reference import topic_sides as ref
+    return ref(theta.contiguous(), phi.contiguous(), i32(doc), i32(word)), "cpu"
+
+
 def rank_hosts(min_score: torch.Tensor, flagged: torch.Tensor, limit: Optional[int] = None) -> np.ndarray:
     """Document rows with at least one flagged side, ascending by their lowest score, ties to the lowest row
     (int64 host array); ``limit``: only the first ``limit`` of them (the MAXRESULTS radix select and its tie
