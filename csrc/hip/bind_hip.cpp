@@ -272,6 +272,15 @@ PYBIND11_MODULE(_onihip, m) {
     oni::launch_topic_sides(a, max_blocks, S(stream));
   });
 
+  m.def("column_l1_width_max", []() { return oni::kColumnL1WidthMax; });
+  m.def("column_l1_tile", [](int W) { return oni::column_l1_tile(W); });
+  m.def("column_l1", [](u A, u B, int64_t Va, int64_t Vb, int Wa, int Wb, u ia, u ib, int64_t M, int64_t block,
+                        int64_t b0, int64_t nb, u scratch, u C, bool first, int max_blocks, u stream) {
+    oni::ColumnL1Args a{P<const double>(A), P<const double>(B), Va, Vb, Wa, Wb, P<const int64_t>(ia),
+                        P<const int64_t>(ib), M, block, b0, nb, P<double>(scratch), P<double>(C), first ? 1 : 0};
+    oni::launch_column_l1(a, max_blocks, S(stream));
+  });
+
   m.def("holdout_draw", [](u base, u counts, u chunk_off, int64_t nnz, int64_t chunks, unsigned long long key,
                            unsigned long long thr, int lane_tokens, u t, int max_blocks, u stream) {
     oni::HoldoutDrawArgs a{P<const int64_t>(base), P<const int64_t>(counts), P<const int64_t>(chunk_off), nnz, chunks,

@@ -489,6 +489,30 @@ struct TopicSidesArgs {
 };
 void launch_topic_sides(const TopicSidesArgs& a, int max_blocks, hipStream_t s);
 
+// --topic-match (column_l1.hip).  column_l1: C[a][b] = the sum over the M pairs of |A[ia[m]][a] - B[ib[m]][b]| (ia
+// and ib null: the identity).  The pairs are cut into blocks of `block`; a block is summed from 0.0 in pair order
+// (one rounded subtraction, its magnitude, one rounded add), the block sums are added from 0.0 in block order.  A
+// NaN difference makes the sum NaN.  One launch handles the blocks b0 .. b0 + nb - 1 and continues C from the
+// batch before it (first: from 0.0): the same sequence of adds for every batch size, no atomics.
+constexpr int kColumnL1WidthMax = 1 << 15;   // largest Wa / Wb
+struct ColumnL1Args {
+  const double* A;       // [Va][Wa]
+  const double* B;       // [Vb][Wb]
+  int64_t Va, Vb;
+  int Wa, Wb;            // 1 .. kColumnL1WidthMax
+  const int64_t* ia;     // [M] rows of A, or null with ib: pair m is row m of both (bounds checked on the host)
+  const int64_t* ib;     // [M] rows of B
+  int64_t M;             // pairs, 0 <= M < 2^40
+  int64_t block;         // pairs of a block, 1 .. 2^31 - 1
+  int64_t b0, nb;        // the launch's blocks: 0 <= b0, b0 + nb <= ceil(M / block)
+  double* scratch;       // [nb][Wa][Wb]
+  double* C;             // [Wa][Wb]
+  int first;             // 1: the sums start at 0.0; 0: they continue from C
+};
+// max_blocks: cap on the workgroups per launch (0: 65536)
+void launch_column_l1(const ColumnL1Args& a, int max_blocks, hipStream_t s);
+int column_l1_tile(int W);   // columns of a tile along a side of W columns (32 or 64)
+
 // --holdout (holdout.hip).  holdout_draw: t[e] = the tokens j of CSR entry e, 0 <= j < counts[e], with
 // splitmix64(key ^ (base[e] + j)) >> 11 < thr -- integers only, so t depends on nothing but (key, thr, corpus).
 // An entry of at most lane_tokens tokens is drawn by one lane; a longer one is cut into chunks of

@@ -11,11 +11,13 @@
 #include <algorithm>
 #include <atomic>
 #include <charconv>
+#include <cmath>
 #include <cstring>
 #include <limits>
 #include <thread>
 
 #include "../common/splitmix64.h"
+#include "assign.h"
 #include "corpus_io.h"
 #include "dns.h"
 #include "engine_plan.h"
@@ -424,6 +426,23 @@ PYBIND11_MODULE(_oninative, m) {
     std::vector<std::string> out;
     out.reserve(a.size());
     for (py::ssize_t i = 0; i < a.size(); ++i) out.push_back(java_double(a.data()[i]));
+    return out;
+  });
+
+  // --topic-match: the permutation of least total cost of a square matrix (assign.h); a NaN cost counts as nan_cost
+  m.def("assign_min", [](py::array_t<double, py::array::c_style | py::array::forcecast> cost, double nan_cost) {
+    if (cost.ndim() != 2 || cost.shape(0) != cost.shape(1)) throw py::value_error("assign_min: cost must be [n, n]");
+    const int64_t n = cost.shape(0);
+    for (py::ssize_t i = 0; i < cost.size(); ++i)
+      if (std::isinf(cost.data()[i])) throw py::value_error("assign_min: an infinite cost");
+    if (!std::isfinite(nan_cost)) throw py::value_error("assign_min: nan_cost must be finite");
+    py::array_t<int64_t> out(n);
+    const double* c = cost.data();
+    int64_t* o = out.mutable_data();
+    {
+      py::gil_scoped_release rel;
+      oni::assign_min(c, n, nan_cost, o);
+    }
     return out;
   });
 

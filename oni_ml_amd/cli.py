@@ -95,13 +95,15 @@ def clean_workdir(lpath: str):
     what an earlier --explain, --expect or --tail run left, ``<type>_explain.csv``, ``word_fields.npz``,
     ``<type>_expect.csv`` and ``<type>_tail.csv``, and an earlier --peers run's ``<type>_peers.csv`` and
     ``<type>_peer_groups.csv``, and an earlier --topic-report run's ``<type>_topics.csv``, ``<type>_topic_words.csv``,
-    ``<type>_topic_hosts.csv`` and ``<type>_topic.csv``: a fresh run removes them with or without the flags, since their
+    ``<type>_topic_hosts.csv`` and ``<type>_topic.csv``, and an earlier --topic-match run's
+    ``<type>_topic_match.csv``, ``<type>_topic_stability.csv`` and ``<type>_host_drift.csv``: a fresh run removes them with or without the flags, since their
     lines would not describe this run's results file.  ``ensemble/`` and ``holdout/`` (an earlier run's members, its
     held-out records and training fits) go too."""
     for pat in ("*.dat", "*.beta", "*.gamma", "*.other", "*.pkl", "checkpoint.npz", "final_model.npz",
                 "final_gamma.rank*.npz", "word_fields.npz", "*_explain.csv", "*_expect.csv",
                 "*_tail.csv", "*_peers.csv", "*_peer_groups.csv", "*_topics.csv", "*_topic_words.csv",
-                "*_topic_hosts.csv", "*_topic.csv"):
+                "*_topic_hosts.csv", "*_topic.csv", "*_topic_match.csv", "*_topic_stability.csv",
+                "*_host_drift.csv"):
         for f in glob.glob(os.path.join(lpath, pat)):
             os.unlink(f)
     shutil.rmtree(os.path.join(lpath, ".stages"), ignore_errors=True)
@@ -150,6 +152,16 @@ def cmd_ml_ops(argv):
                          "that carry it) and <type>_topic.csv, line for line with the results file: the topic that "
                          "explains every written side and its share of the side's score (1 <= N <= 32; 0 or "
                          "TOPIC_REPORT unset: off; one process only)")
+    ap.add_argument("--topic-match", action="store_true", default=None,
+                    help="also write <type>_topic_match.csv and <type>_topic_stability.csv: the topics of every other "
+                         "--ensemble member matched to member 0's by the total-variation distance of their word "
+                         "distributions (a minimum-cost assignment), and per topic how stable it is across the members "
+                         "(or TOPIC_MATCH=1; one process only)")
+    ap.add_argument("--topic-match-day", default=None, metavar="DIR",
+                    help="also match the model of a previous run (DIR: its work directory, with doc_results.csv and "
+                         "word_results.csv) to today's topics, words joined by name, and write <type>_host_drift.csv: "
+                         "per host of both days how far its topic mixture moved, in today's topic numbering.  Implies "
+                         "--topic-match (or TOPIC_MATCH_DAY; one process only)")
     ap.add_argument("--holdout", type=float, default=None, metavar="F",
                     help="hold the fraction F (0 < F <= 0.5) of every document's tokens out, fit on the rest and write "
                          "the held-out perplexity per topic count to <LPATH>/holdout/ (or HOLDOUT; one process only)")
@@ -210,7 +222,8 @@ def cmd_ml_ops(argv):
                            rank_gamma=a.rank_gamma, verbose=not a.quiet, cuts=a.cuts, hdfs=a.hdfs or None,
                            hadoop=a.hadoop, host_report=a.host_report, ensemble=a.ensemble, explain=a.explain,
                            expect=a.expect, tail=a.tail, tail_tol=a.tail_tol, peers=a.peers,
-                           topic_report=a.topic_report, holdout=a.holdout,
+                           topic_report=a.topic_report, topic_match=a.topic_match,
+                           topic_match_day=a.topic_match_day, holdout=a.holdout,
                            holdout_topics=a.holdout_topics, holdout_select=a.holdout_select)
     # --ensemble / ENSEMBLE (the site file and the environment set it too): refused here, before anything is
     # written and before a process group is asked for
@@ -231,6 +244,9 @@ def cmd_ml_ops(argv):
     CFG.RunConfig.check_peers(first.peers, a.gpus, a.hdfs, int(os.environ.get("WORLD_SIZE", "1")))
     # --topic-report / TOPIC_REPORT likewise
     CFG.RunConfig.check_topic_report(first.topic_report, a.gpus, a.hdfs, int(os.environ.get("WORLD_SIZE", "1")))
+    # --topic-match / TOPIC_MATCH and --topic-match-day / TOPIC_MATCH_DAY likewise
+    CFG.RunConfig.check_topic_match(first.topic_match, first.topic_match_day, first.lpath, a.gpus, a.hdfs,
+                                    int(os.environ.get("WORLD_SIZE", "1")))
     # --holdout / HOLDOUT likewise
     CFG.RunConfig.check_holdout(first.holdout, first.holdout_list(), first.holdout_select, a.start, a.compat, a.dsource,
                                 a.backend, a.gpus, a.hdfs, int(os.environ.get("WORLD_SIZE", "1")))

@@ -28,7 +28,7 @@ from .models.lda.settings import LDASettings
 ENV_KEYS = ("FLOW_PATH", "DNS_PATH", "PROXY_PATH", "HPATH", "LPATH", "LUSER", "TOL", "DUPFACTOR", "KRB_AUTH", "NODES",
             "UINODE", "RPATH", "LDAPATH", "SPK_EXEC", "SPK_EXEC_MEM", "TOP1M", "CUT", "MAXRESULTS", "ENSEMBLE", "EXPLAIN",
             "HOLDOUT", "HOLDOUT_TOPICS", "TAIL", "TAIL_TOL", "EXPECT", "PEERS",
-            "TOPIC_REPORT")
+            "TOPIC_REPORT", "TOPIC_MATCH", "TOPIC_MATCH_DAY")
 
 # proxy has no multi-rank, sharded or HDFS-staged form
 PROXY_ONE_PROCESS = "proxy runs on one process: launch it without torchrun, with --gpus 1 and without --hdfs"
@@ -89,6 +89,17 @@ TOPIC_SCRATCH_MB = 256
 # rows of the strided sample whose N-th value per column lets the pass over all rows skip what lies below it (a
 # table of fewer than twice as many rows is not sampled).  No bit of the result depends on it either
 TOPIC_SAMPLE = 8192
+
+# topics are matched from one process's whole phi and theta tables: no multi-rank, sharded or HDFS-staged form
+TOPIC_MATCH_ONE_PROCESS = ("--topic-match runs on one process: launch it without torchrun, with --gpus 1 and "
+                           "without --hdfs")
+# pairs of one block of ops.hip.column_l1 / ops.reference.column_l1.  The block sums are added in block order, so
+# the value is part of the bits of every distance, as GROUP_BLOCK is of a group sum (the reasoning, and what is not
+# measured yet: profiles/topic_match.md)
+MATCH_BLOCK = 1024
+# cap on the blocks' partials of ops.hip.column_l1 (Wa x Wb x 8 bytes per block; more blocks: batches that continue
+# the running sums).  It changes no bit of the result
+MATCH_SCRATCH_MB = 256
 
 # --holdout: the split and the K fits are one process's: no multi-rank, sharded or HDFS-staged form
 HOLDOUT_ONE_PROCESS = "--holdout runs on one process: launch it without torchrun, with --gpus 1 and without --hdfs"
@@ -172,6 +183,12 @@ class RunConfig:
                                           # <type>_topic_words.csv, <type>_topic_hosts.csv (the N words and hosts that
                                           # carry every topic) and <type>_topic.csv (the topic that explains every
                                           # written side); 1 <= N <= TOPIC_REPORT_MAX; 0: off
+    topic_match: bool = False             # --topic-match / TOPIC_MATCH: also write <type>_topic_match.csv and
+                                          # <type>_topic_stability.csv, the topics of an ensemble's members (and of
+                                          # topic_match_day's model) aligned to member 0's
+    topic_match_day: str = ""             # --topic-match-day / TOPIC_MATCH_DAY: the work directory of a previous run
+                                          # whose model is aligned too, with <type>_host_drift.csv; implies
+                                          # topic_match
     holdout: float = 0.0                  # --holdout / HOLDOUT: hold this fraction of every document's tokens out, fit
                                           # on the rest and report the held-out perplexity per topic count; 0: off
     holdout_topics: str = ""              # --holdout-topics / HOLDOUT_TOPICS: "K1,K2,..." to evaluate; "": topics alone
@@ -261,6 +278,8 @@ class RunConfig:
             raise ValueError(TAIL_ONE_PROCESS)
         self.peers = self.check_peers(self.peers, self.gpus, self.hdfs)
         self.topic_report = self.check_topic_report(self.topic_report, self.gpus, self.hdfs)
+        self.topic_match = self.check_topic_match(self.topic_match, self.topic_match_day, self.lpath, self.gpus,
+                                                  self.hdfs)
         self.check_ensemble(self.ensemble, self.start, self.gpus, self.hdfs)
         self.check_holdout(self.holdout, self.holdout_list(), self.holdout_select, self.start, self.compat,
                            self.dsource, self.backend, self.gpus, self.hdfs)
@@ -301,6 +320,25 @@ class RunConfig:
         if gpus > 1 or hdfs or world > 1:
             raise ValueError(TOPIC_REPORT_ONE_PROCESS)
         return n
+
+    @staticmethod
+    def check_topic_match(on, day: str = "", lpath: str = "", gpus: int = 1, hdfs: bool = False,
+                          world: int = 1) -> bool:
+        """The --topic-match / --topic-match-day rules, also applied by the command line before anything is written:
+        one process; the day's directory holds both results files and is not the work directory itself."""
+        day = str(day or "")
+        if not on and not day:
+            return False
+        if gpus > 1 or hdfs or world > 1:
+            raise ValueError(TOPIC_MATCH_ONE_PROCESS)
+        if day:
+            for f in ("doc_results.csv", "word_results.csv"):
+                if not os.path.isfile(os.path.join(day, f)):
+                    raise ValueError(f"--topic-match-day: {os.path.join(day, f)} not found: the directory must hold "
+                                     f"a finished run's doc_results.csv and word_results.csv")
+            if lpath and os.path.realpath(day) == os.path.realpath(lpath):
+                raise ValueError(f"--topic-match-day: {day} is this run's own work directory (LPATH)")
+        return True
 
     @staticmethod
     def check_holdout(holdout: float, topics: List[int], select: bool, start: str, compat: str, dsource: str,
@@ -414,6 +452,10 @@ def _apply(cfg: RunConfig, layer: Dict[str, object]):
         cfg.peers = int(layer["PEERS"])
     if "TOPIC_REPORT" in layer and layer["TOPIC_REPORT"] not in ("", None):
         cfg.topic_report = int(layer["TOPIC_REPORT"])
+    if "TOPIC_MATCH" in layer and layer["TOPIC_MATCH"] not in ("", None):
+        cfg.topic_match = str(layer["TOPIC_MATCH"]).strip().lower() not in ("0", "false", "no", "off")
+    if "TOPIC_MATCH_DAY" in layer and isinstance(layer["TOPIC_MATCH_DAY"], str) and layer["TOPIC_MATCH_DAY"]:
+        cfg.topic_match_day = layer["TOPIC_MATCH_DAY"]
     if "HOLDOUT" in layer and layer["HOLDOUT"] not in ("", None):
         cfg.holdout = float(layer["HOLDOUT"])
     if "HOLDOUT_TOPICS" in layer and layer["HOLDOUT_TOPICS"] not in ("", None):

@@ -1074,6 +1074,88 @@ def topic_sides(theta3, phi3, doc, word, max_blocks: int = 0):
     return col, resp, share, ht
 
 
+def column_l1_path(Wa: int, Wb: int) -> str:
+    """The output tile of the column_l1 kernel at these widths (csrc/hip/column_l1.hip): ``tile<TA>x<TB>``, 32 or
+    64 columns each way (2 or 4 per lane)."""
+    L = lib()
+    return f"tile{L.column_l1_tile(int(Wa))}x{L.column_l1_tile(int(Wb))}"
+
+
+def column_l1(A, B, ia=None, ib=None, block=None, max_blocks: int = 0, scratch_mb=None):
+    """The L1 distances between the columns of two tables (csrc/hip/column_l1.hip; ``ops.reference.column_l1`` is
+    the twin): float64 [Wa, Wb] as a new device tensor, ``C[a, b]`` = the sum over the M pairs of
+    ``|A[ia[m], a] - B[ib[m], b]|``.
+
+    ``A`` [Va, Wa] / ``B`` [Vb, Wb] float64; ``ia`` / ``ib`` int64 [M] rows, both None: the identity
+    (Va == Vb == M).  The pairs are cut into blocks of ``block`` consecutive pairs (``config.MATCH_BLOCK``); within
+    a block, from 0.0 in pair order, one rounded subtraction, its magnitude, one rounded add; the block sums are
+    added from 0.0 in block order -- the block size is part of the result, the grid and the batches are not.  A NaN
+    difference makes the sum NaN; no atomics.
+
+    The blocks' partials (Wa x Wb x 8 bytes each) live in a scratch of at most ``scratch_mb`` MiB
+    (``config.MATCH_SCRATCH_MB``): more blocks than fit run in batches, each continuing the running sums of the one
+    before -- the same sequence of adds.  Everything is checked on the host before a launch (host reads: the bounds
+    of the indices); ``M == 0`` launches nothing.  ``max_blocks``: cap on the workgroups per launch (tests: a small
+    cap makes the grid-stride loops wrap)."""
+    import operator
+    _max_blocks(max_blocks)
+    MB = operator.index(_CFG.MATCH_BLOCK if block is None else block)
+    if MB < 1 or MB >= 1 << 31:
+        raise ValueError(f"column_l1: block must be in [1, 2^31), got {MB}")
+    cap_mb = float(_CFG.MATCH_SCRATCH_MB if scratch_mb is None else scratch_mb)
+    if not cap_mb > 0:
+        raise ValueError(f"column_l1: scratch_mb must be > 0, got {scratch_mb!r}")
+    for name, t in (("A", A), ("B", B)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 2:
+            raise ValueError(f"{name}: expected a [rows, W] tensor")
+        if t.dtype != torch.float64:
+            raise ValueError(f"{name}: expected torch.float64, got {t.dtype}")
+        if not t.is_cuda:
+            raise ValueError(f"{name}: must be a GPU tensor")
+        if not t.is_contiguous():
+            raise ValueError(f"{name}: must be contiguous")
+    dev = A.device
+    if B.device != dev:
+        raise ValueError(f"B: on {B.device}, expected {dev}")
+    (Va, Wa), (Vb, Wb) = (int(x) for x in A.shape), (int(x) for x in B.shape)
+    if (ia is None) != (ib is None):
+        raise ValueError("column_l1: ia and ib go together (both None: the identity)")
+    if ia is None:
+        if Va != Vb:
+            raise ValueError(f"column_l1: the identity form needs tables of equal height, got {Va} and {Vb}")
+        M, p_ia, p_ib = Va, 0, 0
+    else:
+        if not isinstance(ia, torch.Tensor) or ia.dim() != 1:
+            raise ValueError("ia: expected a 1-D tensor")
+        if not isinstance(ib, torch.Tensor) or ib.dim() != 1:
+            raise ValueError("ib: expected a 1-D tensor")
+        M = ia.numel()
+        if ib.numel() != M:
+            raise ValueError(f"column_l1: ia has {M} rows, ib {ib.numel()}")
+        p_ia = _index("ia", ia, torch.int64, (M,), dev)
+        p_ib = _index("ib", ib, torch.int64, (M,), dev)
+    L = lib()
+    if max(Wa, Wb) > L.column_l1_width_max() or M >= 1 << 40:
+        raise ValueError(f"column_l1: {Wa} x {Wb} columns, {M} pairs (W <= {L.column_l1_width_max()}, M < 2^40)")
+    out = torch.zeros((Wa, Wb), dtype=torch.float64, device=dev)
+    if M == 0 or Wa == 0 or Wb == 0:
+        return out
+    # index bounds (host check before a gather kernel touches memory)
+    if ia is not None:
+        if int(ia.min()) < 0 or int(ia.max()) >= Va:
+            raise ValueError("ia: index out of range")
+        if int(ib.min()) < 0 or int(ib.max()) >= Vb:
+            raise ValueError("ib: index out of range")
+    nblk = -(-M // MB)
+    batch = max(1, min(nblk, int(cap_mb * (1 << 20)) // (8 * Wa * Wb)))
+    scratch = torch.empty(batch * Wa * Wb, dtype=torch.float64, device=dev)
+    for b0 in range(0, nblk, batch):
+        L.column_l1(A.data_ptr(), B.data_ptr(), Va, Vb, Wa, Wb, p_ia, p_ib, int(M), int(MB), int(b0),
+                    int(min(batch, nblk - b0)), scratch.data_ptr(), out.data_ptr(), b0 == 0, int(max_blocks),
+                    _stream())
+    return out
+
+
 def holdout_draw(doc_ptr, counts, seed, thr, max_blocks: int = 0, rules: bool = True, lane_tokens=None):
     """Held-out tokens of every CSR entry (csrc/hip/holdout.hip; ``ops.reference.holdout_draw`` is the twin): int64
     [nnz] as a new device tensor.

@@ -76,6 +76,22 @@ def engine_plan(doc_ptr, word_idx, counts, V: int, KS: int, U: int, buf, *, edge
                              float(stage_cap), int(umax), int(iso_m), int(xcds), bool(defer_final), buf, int(threads))
 
 
+ASSIGN_NAN_COST = 2.0      # what a NaN cost counts as in assign_min: above any total-variation distance
+
+
+def assign_min(cost):
+    """The permutation of least total cost (csrc/native/assign.h, an O(n^3) shortest-augmenting-path Hungarian
+    method): ``cost`` square float64 [n, n], every entry finite or NaN; returns int64 [n], ``match[i]`` the column
+    of row i.  A NaN cost counts as ``ASSIGN_NAN_COST``.  Deterministic: the scans run in column order with strict
+    comparisons, so the same input bits give the same permutation.  A rectangular problem is padded to square with
+    0.0-cost dummy rows / columns by the caller."""
+    import numpy as np
+    c = np.ascontiguousarray(cost, np.float64)
+    if c.ndim != 2 or c.shape[0] != c.shape[1]:
+        raise ValueError(f"assign_min: cost must be square [n, n], got shape {c.shape}")
+    return lib().assign_min(c, ASSIGN_NAN_COST)
+
+
 def available() -> bool:
     try:
         lib()

@@ -570,6 +570,66 @@ def topic_sides(theta3, phi3, doc, word, slab: int = TOPIC_SLAB):
     return col, resp, share, ht
 
 
+MATCH_SLAB = 1 << 22      # doubles of the [blocks, Wa, Wb] partials the column_l1 twin holds at a time
+
+
+def column_l1(A, B, ia=None, ib=None, block=None, slab: int = MATCH_SLAB):
+    """Torch twin of ``ops.hip.column_l1`` (csrc/hip/column_l1.hip) on any device, bit for bit, and the CPU
+    pipeline's path: float64 [Wa, Wb], ``C[a, b]`` = the sum over the M pairs of ``|A[ia[m], a] - B[ib[m], b]|``.
+    ``A`` [Va, Wa] / ``B`` [Vb, Wb] float64; ``ia`` / ``ib`` [M] rows, both None: the identity (Va == Vb == M).
+    The pairs are cut into blocks of ``block`` consecutive pairs (``config.MATCH_BLOCK``); within a block, from 0.0
+    in pair order, one rounded subtraction, its magnitude, one rounded add; the block sums are added from 0.0 in
+    block order.  A NaN difference (inf - inf among them) makes the sum NaN; M = 0 gives zeros.  The blocks are
+    taken in slabs of at most ``slab`` / (Wa Wb): a loop over the position within the block (a position that a
+    block does not have adds +0.0, which moves no bit of a sum that is never -0.0), then a loop over the slab's
+    blocks in order, which continues the running sum."""
+    from ..config import MATCH_BLOCK
+    MB = int(MATCH_BLOCK if block is None else block)
+    if MB < 1:
+        raise ValueError(f"column_l1: block must be >= 1, got {MB}")
+    for name, t in (("A", A), ("B", B)):
+        if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.dtype != torch.float64:
+            raise ValueError(f"column_l1: {name} must be a [rows, W] float64 tensor")
+    if A.device != B.device:
+        raise ValueError(f"column_l1: A on {A.device}, B on {B.device}")
+    if (ia is None) != (ib is None):
+        raise ValueError("column_l1: ia and ib go together")
+    dev = A.device
+    (Va, Wa), (Vb, Wb) = (int(x) for x in A.shape), (int(x) for x in B.shape)
+    if ia is None:
+        if Va != Vb:
+            raise ValueError(f"column_l1: the identity form needs tables of equal height, got {Va} and {Vb}")
+        M = Va
+    else:
+        ia, ib = ia.reshape(-1).to(torch.int64), ib.reshape(-1).to(torch.int64)
+        M = ia.numel()
+        if ib.numel() != M:
+            raise ValueError("column_l1: ia and ib differ in length")
+        if M and (int(ia.min()) < 0 or int(ia.max()) >= Va or int(ib.min()) < 0 or int(ib.max()) >= Vb):
+            raise ValueError("column_l1: index out of range")
+    out = torch.zeros((Wa, Wb), dtype=torch.float64, device=dev)
+    if M == 0 or Wa == 0 or Wb == 0:
+        return out
+    nblk = -(-M // MB)
+    step = max(1, int(slab) // (Wa * Wb))
+    zero = torch.zeros((), dtype=torch.float64, device=dev)
+    for s0 in range(0, nblk, step):
+        nb = min(step, nblk - s0)
+        start = (s0 + torch.arange(nb, device=dev)) * MB
+        b_len = torch.clamp(M - start, max=MB)
+        part = torch.zeros((nb, Wa, Wb), dtype=torch.float64, device=dev)
+        for m in range(int(b_len.max())):
+            have = b_len > m
+            pos = torch.where(have, start + m, torch.zeros_like(start))
+            ra = A[pos if ia is None else ia[pos]]
+            rb = B[pos if ib is None else ib[pos]]
+            t = ra.unsqueeze(2) - rb.unsqueeze(1)                       # rounded difference, then rounded sum
+            part = part + torch.where(have.reshape(nb, 1, 1), t.abs(), zero)
+        for k in range(nb):
+            out = out + part[k]
+    return out
+
+
 def select_lowest(key, flag, limit, with_count: bool = False):
     """Torch twin of ``ops.hip.select_lowest`` (csrc/hip/select_lowest.hip) on any device: the row indices
     (int64, ascending) of the ``limit`` flagged rows that a stable ascending sort of their keys puts first, all

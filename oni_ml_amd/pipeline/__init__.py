@@ -26,6 +26,9 @@ def run(cfg, dist=None, device=None, log=print) -> dict:
     if cfg.topic_report and dist is not None and dist.active:
         from ..config import TOPIC_REPORT_ONE_PROCESS
         raise ValueError(TOPIC_REPORT_ONE_PROCESS)
+    if (cfg.topic_match or cfg.topic_match_day) and dist is not None and dist.active:
+        from ..config import TOPIC_MATCH_ONE_PROCESS
+        raise ValueError(TOPIC_MATCH_ONE_PROCESS)
     if cfg.holdout > 0 and dist is not None and dist.active:
         from ..config import HOLDOUT_ONE_PROCESS
         raise ValueError(HOLDOUT_ONE_PROCESS)

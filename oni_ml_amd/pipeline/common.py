@@ -1130,6 +1130,240 @@ def write_topic_report(cfg, tables, order, key, sides, ex: ExplainInput, cols, s
                 topic_resp_hist=dict(zip(TOPIC_RESP_BUCKETS + ("none",), hist.tolist() + [int(has.size - has.sum())])))
 
 
+DRIFT_DECADES = ("<1e-6", "<1e-5", "<1e-4", "<1e-3", "<1e-2", "<1e-1", "<=1")
+TOPIC_MATCH_KEYS = ("topic_match", "topic_match_day", "topic_match_pairs", "topic_match_shared_words",
+                    "topic_match_shared_hosts", "topic_match_new_hosts", "topic_match_mutual", "topic_match_path",
+                    "host_drift_hist")
+TOPIC_MATCH_FILES = ("topic_match", "topic_stability", "host_drift")      # <type>_<name>.csv
+
+
+def match_topics(cost: np.ndarray):
+    """The alignment of one other model to today's topics from ``cost`` [K, K'] (today's topic a, the other's topic
+    b; a NaN: no distance): ``(match int64 [K'], nearest int64 [K'], mutual bool [K'])``.  ``match[b]``: today's
+    topic of b under the minimum-cost assignment (``native.assign_min`` over the matrix padded to square with
+    0.0-cost dummy rows / columns; -1: b went to a dummy, unmatched).  ``nearest[b]``: the a of lowest cost, ties to
+    the lower a, a NaN never (-1: none).  ``mutual[b]``: b is matched to a, a is its nearest, and b is the
+    lowest-cost column of row a, ties to the lower b."""
+    from ..ops import native
+    K, Kp = cost.shape
+    n = max(K, Kp)
+    sq = np.zeros((n, n), np.float64)
+    sq[:K, :Kp] = cost
+    row_to_col = np.asarray(native.assign_min(sq), np.int64)
+    match = np.full(Kp, -1, np.int64)
+    a = np.arange(K)
+    real = row_to_col[:K] < Kp
+    match[row_to_col[:K][real]] = a[real]
+    far = np.where(np.isnan(cost), np.inf, cost)
+    nearest = np.where(np.isfinite(far).any(0), far.argmin(0), -1).astype(np.int64) if K else np.full(Kp, -1, np.int64)
+    best_col = far.argmin(1) if Kp else np.full(K, -1, np.int64)      # of every row a: the first lowest column
+    b = np.arange(Kp)
+    mutual = (match >= 0) & (nearest == match) & (best_col[np.clip(match, 0, None)] == b if K else False)
+    return match, nearest, mutual
+
+
+def write_topic_match(cfg, tables, ex: ExplainInput, sep: str = ",", log=print) -> dict:
+    """--topic-match / --topic-match-day DIR: the topics of the other models aligned to today's member 0, next to
+    the results file.  The others: the --ensemble members ``m1``, ``m2``, ... and, with DIR, ``prev`` -- member 0
+    of ``load_model_tables(DIR)``.
+
+    Distances (``scorer.column_l1``: per pair of columns the sum of |x - y| over the paired rows, in blocks of
+    ``config.MATCH_BLOCK``).  A member shares today's rows: ``cost[a][b] = C[a][b] * 0.5``, the total-variation
+    distance of φ₀'s topic a and the member's topic b.  The previous day's words are joined by name through the
+    name -> row maps of ``ModelTables`` (a name that repeats takes the row its map gives it): today's rows whose
+    name the previous day knows, in row order, give the pairs; ``cost[a][b] = ((C[a][b] + ua[a]) + ub[b]) * 0.5``
+    with ua / ub the column's φ total over its own rows whose name the other day lacks (``scorer.group_rows_sum``,
+    one segment in row order).  No shared word: every distance is 1.0.
+
+    ``<type>_topic_match.csv``, a line per (other, its topic b): other, topic, ``match`` (today's topic; empty:
+    unmatched), ``dist``, ``nearest``, ``nearest_dist``, ``mutual`` (``match_topics``), ``shared_mass`` (the
+    column's φ total over its rows whose name today knows; a member: over all rows).
+    ``<type>_topic_stability.csv``, a line per topic a of today: topic, ``members`` (R - 1), ``members_mutual``,
+    ``mean_dist`` and ``max_dist`` (over the members' matched distances, the adds from 0.0 in member order, one
+    division; empty at R = 1), ``prev_topic``, ``prev_dist``, ``prev_mutual``, ``shared_mass`` (empty without DIR).
+    ``<type>_host_drift.csv`` (with DIR), a line per host of both days, joined by name: host, ``drift``, ``topic``
+    (today's dominant), ``prev_topic`` (the previous day's dominant in today's numbering; empty: unmatched);
+    descending by ``drift``, ties in today's row order.  ``drift``: from 0.0 over today's topics a in order
+    |θ₀[d][a] - θ'[d'][b(a)]| (an unmatched a: against 0.0), then the previous day's unmatched topics in their
+    order, each one rounded subtraction, its magnitude and one rounded add; then * 0.5.  Returns the summary
+    entries."""
+    from ..ops import native
+    from ..ops import sortgroup as SG
+    from ..score import scorer as S
+    theta, phi = S.model_tables3(ex.model)
+    dev = phi.device
+    V, R, K = (int(x) for x in phi.shape)
+    D = int(theta.shape[0])
+    fmt = native.lib().java_double_array
+    phi0 = phi[:, 0, :].contiguous()
+    theta0 = theta[:, 0, :].contiguous()
+
+    def doubles(x):      # a column's own values as its dictionary, empty cells for NaN
+        x = np.ascontiguousarray(x, np.float64)
+        have = ~np.isnan(x)
+        idx = np.full(x.size, -1, np.int32)
+        idx[have] = np.arange(int(have.sum()), dtype=np.int32)
+        return ("dict", fmt(x[have]), idx)
+
+    def ints(x):         # -1: an empty cell
+        x = np.asarray(x, np.int64)
+        ux, x_inv = np.unique(x[x >= 0], return_inverse=True)
+        idx = np.full(x.size, -1, np.int32)
+        idx[x >= 0] = x_inv.astype(np.int32)
+        return ("dict", [str(int(v)) for v in ux], idx)
+
+    def path_of(name):
+        return os.path.join(cfg.lpath, f"{cfg.dsource}_{name}.csv")
+
+    def total(table, rows):      # [W]: the column totals over ``rows`` (ascending) in row order
+        if rows.numel() == 0:
+            return torch.zeros(int(table.shape[1]), dtype=torch.float64, device=dev)
+        return S.group_rows_sum(table, rows.to(torch.int32), torch.zeros(1, dtype=torch.int64, device=dev),
+                                torch.full((1,), rows.numel(), dtype=torch.int64, device=dev)).reshape(-1)
+
+    def rows_t(rows):
+        return torch.from_numpy(np.asarray(rows, np.int64)).to(dev)
+
+    others, path, work = [], "cpu", []      # (label, cost [K, K'] on the host, shared_mass [K'])
+    if R > 1:
+        C, path = S.column_l1(phi0, phi.reshape(V, R * K))
+        cost = (C * 0.5).cpu().numpy()
+        mass = total(phi.reshape(V, R * K), torch.arange(V, device=dev)).cpu().numpy()
+        for r in range(1, R):
+            others.append((f"m{r}", cost[:, r * K:(r + 1) * K], mass[r * K:(r + 1) * K], V))
+        work.append(f"{V} x {K} x {R * K}")
+    prev = None
+    if cfg.topic_match_day:
+        pt = load_model_tables(cfg.topic_match_day)
+        Kp = int(pt.phi.shape[1])
+        phi_p = torch.from_numpy(np.ascontiguousarray(pt.phi, np.float64)).to(dev)
+        today_w, prev_w = tables.word_index(), pt.word_index()
+        names = tables.word_names
+        shared = np.fromiter((nm in prev_w for nm in names), dtype=bool, count=len(names))
+        ia = np.fromiter((today_w[names[r]] for r in np.flatnonzero(shared)), dtype=np.int64, count=int(shared.sum()))
+        ib = np.fromiter((prev_w[names[r]] for r in np.flatnonzero(shared)), dtype=np.int64, count=int(shared.sum()))
+        known = np.fromiter((nm in today_w for nm in pt.word_names), dtype=bool, count=len(pt.word_names))
+        M = int(ia.size)
+        mass_a = total(phi0, rows_t(np.flatnonzero(shared)))
+        mass_b = total(phi_p, rows_t(np.flatnonzero(known)))
+        if M:
+            C, path = S.column_l1(phi0, phi_p, rows_t(ia), rows_t(ib))
+            ua = total(phi0, rows_t(np.flatnonzero(~shared)))
+            ub = total(phi_p, rows_t(np.flatnonzero(~known)))
+            cost = (((C + ua.unsqueeze(1)) + ub.unsqueeze(0)) * 0.5).cpu().numpy()
+        else:
+            log(f"{cfg.dsource}_post: {cfg.topic_match_day} shares no word with this run: every distance is 1.0")
+            cost = np.ones((K, Kp), np.float64)
+        others.append(("prev", cost, mass_b.cpu().numpy(), M))
+        work.append(f"{M} x {K} x {Kp}")
+        prev = (pt, Kp, mass_a.cpu().numpy())
+
+    # <type>_topic_match.csv
+    labels, col_other, col_b, col_match, col_dist, col_near, col_ndist, col_mut, col_mass = [], [], [], [], [], [], [], [], []
+    aligned = []      # per other: (match [K'], mutual [K'], cost)
+    for i, (label, cost, mass, _) in enumerate(others):
+        match, nearest, mutual = match_topics(cost)
+        Kp = cost.shape[1]
+        b = np.arange(Kp)
+        labels.append(label)
+        col_other.append(np.full(Kp, i, np.int32))
+        col_b.append(b)
+        col_match.append(match)
+        col_dist.append(np.where(match >= 0, cost[np.clip(match, 0, None), b], np.nan) if K else np.full(Kp, np.nan))
+        col_near.append(nearest)
+        col_ndist.append(np.where(nearest >= 0, cost[np.clip(nearest, 0, None), b], np.nan) if K else np.full(Kp, np.nan))
+        col_mut.append(mutual.astype(np.int64))
+        col_mass.append(mass)
+        aligned.append((match, mutual, cost))
+    cat = lambda xs, dt: np.concatenate(xs).astype(dt) if xs else np.zeros(0, dt)      # noqa: E731
+    n_lines = int(sum(x.size for x in col_b))
+    native.lib().write_rows(path_of("topic_match"), None,
+                            [("dict", labels, cat(col_other, np.int32)), ("int", cat(col_b, np.int64)),
+                             ints(cat(col_match, np.int64)), doubles(cat(col_dist, np.float64)),
+                             ints(cat(col_near, np.int64)), doubles(cat(col_ndist, np.float64)),
+                             ("int", cat(col_mut, np.int64)), ("java", cat(col_mass, np.float64))],
+                            sep=sep, threads=cfg.threads, n=n_lines)
+
+    # <type>_topic_stability.csv: today's topics
+    def inverse(match, mutual, cost):      # per today's topic a: its b (-1), the distance (NaN), mutual
+        b_of = np.full(K, -1, np.int64)
+        has = match >= 0
+        b_of[match[has]] = np.flatnonzero(has)
+        ok = b_of >= 0
+        dist = np.where(ok, cost[np.arange(K), np.clip(b_of, 0, None)], np.nan) if cost.shape[1] else np.full(K, np.nan)
+        return b_of, dist, np.where(ok, mutual[np.clip(b_of, 0, None)], False) if cost.shape[1] else np.zeros(K, bool)
+
+    nan_k = np.full(K, np.nan)
+    m_mut, m_sum, m_max = np.zeros(K, np.int64), np.zeros(K, np.float64), np.zeros(K, np.float64)
+    for match, mutual, cost in aligned[:R - 1]:
+        _, dist, mut = inverse(match, mutual, cost)
+        m_mut += mut
+        m_sum = m_sum + dist                                             # from 0.0 in member order
+        m_max = np.where((dist > m_max) | np.isnan(dist), dist, m_max)   # a NaN stays
+    if R > 1:
+        member_cols = [("int", np.full(K, R - 1, np.int64)), ints(m_mut), doubles(m_sum / float(R - 1)), doubles(m_max)]
+    else:
+        member_cols = [("int", np.zeros(K, np.int64)), ints(np.full(K, -1)), doubles(nan_k), doubles(nan_k)]
+    if prev is not None:
+        p_b, p_dist, p_mut = inverse(*aligned[-1])
+        prev_cols = [ints(p_b), doubles(p_dist), ints(np.where(p_b >= 0, p_mut.astype(np.int64), -1)), doubles(prev[2])]
+    else:
+        prev_cols = [ints(np.full(K, -1)), doubles(nan_k), ints(np.full(K, -1)), doubles(nan_k)]
+    native.lib().write_rows(path_of("topic_stability"), None,
+                            [("int", np.arange(K, dtype=np.int64))] + member_cols + prev_cols,
+                            sep=sep, threads=cfg.threads, n=K)
+
+    # <type>_host_drift.csv
+    shared_hosts = new_hosts = None
+    hist = {}
+    if prev is not None:
+        pt, Kp, _ = prev
+        today_d, prev_d = tables.doc_index(), pt.doc_index()
+        dn = tables.doc_names
+        d_rows = np.asarray([d for d, nm in enumerate(dn) if nm in prev_d and today_d[nm] == d], np.int64)
+        p_rows = np.asarray([prev_d[dn[d]] for d in d_rows.tolist()], np.int64)
+        shared_hosts = int(d_rows.size)
+        new_hosts = int(sum(1 for nm in today_d if nm not in prev_d))
+        match = aligned[-1][0]                                           # [K']: today's topic of b, -1
+        b_of = inverse(*aligned[-1])[0]                                  # [K]: the previous topic of a, -1
+        th0 = SG.gather(theta0, rows_t(d_rows))                          # [n, K]
+        thp = SG.gather(torch.from_numpy(np.ascontiguousarray(pt.theta, np.float64)).to(dev), rows_t(p_rows))
+        zero = torch.zeros((), dtype=torch.float64, device=dev)
+        acc = torch.zeros(shared_hosts, dtype=torch.float64, device=dev)
+        for a in range(K):
+            other = thp[:, int(b_of[a])] if b_of[a] >= 0 else zero       # an unmatched topic: its whole entry
+            acc = acc + (th0[:, a] - other).abs()
+        for b in np.flatnonzero(match < 0).tolist():
+            acc = acc + (zero - thp[:, b]).abs()
+        drift = acc * 0.5
+        (dom, _), _ = S.row_dominant(th0.reshape(shared_hosts, 1, K))
+        (dom_p, _), _ = S.row_dominant(thp.reshape(shared_hosts, 1, Kp))
+        dom_p = dom_p.reshape(-1).to(torch.int64)
+        to_today = torch.cat([rows_t(match), torch.full((1,), -1, dtype=torch.int64, device=dev)])
+        prev_topic = SG.gather(to_today, torch.where(dom_p >= 0, dom_p, torch.full_like(dom_p, Kp)))
+        _, perm = torch.sort(SG.f64_order_keys(zero - drift), stable=True)      # descending, ties in row order
+        perm_h = perm.cpu().numpy()
+        drift_h = drift.cpu().numpy()[perm_h]
+        ur, r_inv = np.unique(d_rows[perm_h], return_inverse=True)
+        native.lib().write_rows(path_of("host_drift"), None,
+                                [("dict", [dn[i] for i in ur.tolist()], r_inv.astype(np.int32)), doubles(drift_h),
+                                 ints(dom.reshape(-1).cpu().numpy().astype(np.int64)[perm_h]),
+                                 ints(prev_topic.cpu().numpy()[perm_h])],
+                                sep=sep, threads=cfg.threads, n=shared_hosts)
+        good = drift_h[~np.isnan(drift_h)]
+        edges = np.asarray([1e-6, 1e-5, 1e-4, 1e-3, 1e-2, 1e-1])
+        h = np.bincount(np.searchsorted(edges, good, side="right"), minlength=len(DRIFT_DECADES)).astype(np.int64)
+        hist = dict(zip(DRIFT_DECADES + ("none",), h.tolist() + [int(drift_h.size - good.size)]))
+    log(f"{cfg.dsource}_post: {len(others)} models matched to {K} topics in {path_of('topic_match')} "
+        f"(pairs x Wa x Wb: {', '.join(work) if work else 'none'}; {path})")
+    return dict(topic_match=True, topic_match_day=cfg.topic_match_day or "",
+                topic_match_pairs=[int(o[3]) for o in others],
+                topic_match_shared_words=others[-1][3] if prev is not None else None,
+                topic_match_shared_hosts=shared_hosts, topic_match_new_hosts=new_hosts,
+                topic_match_mutual=[int(m.sum()) for _, m, _ in aligned], topic_match_path=path,
+                host_drift_hist=hist)
+
+
 def one_sided_index(tables, ip_names, ip, unames, inv, device, ip_map=None):
     """The one-sided scorers' (dns, proxy) index set-up: (θ, φ, θ row of every event, φ row of every event).
     ``ip`` / ``inv``: every event's id into ``ip_names`` / ``unames``; ``ip_map``: the doc row of every ip id
@@ -1169,7 +1403,8 @@ def write_results(cfg, tables, what: str, ranked, key, row_cols, events: int, si
     (``ctx``): the ranks' rows merged into one ascending file (``shardio.merge_sorted_rows``, the sortByKey
     shuffle), the counts summed.  ``extra``: further result entries.  ``explain``: the sides' φ rows and columns
     for ``write_explain``, ``write_expect``, ``write_tail``, ``write_peers`` and ``write_topic_report`` (one process,
-    under --explain / --expect / --tail / --peers / --topic-report).
+    under --explain / --expect / --tail / --peers / --topic-report); ``write_topic_match`` (--topic-match) takes
+    the model from it.
     ``tail_rank`` (--tail-tol):
     what ``tail_keys`` returned -- ``ranked`` was made from its key and flag, ``key`` stays the score key that the
     files' columns hold."""
@@ -1205,8 +1440,9 @@ def write_results(cfg, tables, what: str, ranked, key, row_cols, events: int, si
     peers = write_peers(cfg, tables, order, key, sides, explain, cols, sep=sep, log=log) if cfg.peers else {}
     topics = write_topic_report(cfg, tables, order, key, sides, explain, cols, sep=sep,
                                 log=log) if cfg.topic_report else {}
+    matched = write_topic_match(cfg, tables, explain, sep=sep, log=log) if cfg.topic_match else {}
     return dict(flagged=n, below_tol=below, events=events, **(extra or {}), **hosts,
-                **votes_hist(votes, order, cfg.ensemble), **why, **exp, **tail, **peers, **topics,
+                **votes_hist(votes, order, cfg.ensemble), **why, **exp, **tail, **peers, **topics, **matched,
                 **(tail_rank.stats if tail_rank is not None else {}))
 
 

@@ -185,6 +185,10 @@ def run_stages(cfg, spec: PipelineSpec, device=None, log=print) -> dict:
                     topics = {k: res[k] for k in C.TOPIC_REPORT_KEYS}
                     summary.update(topics)
                     R.emit(dict(stage=post_stage + "_detail", **topics))
+                if cfg.topic_match:
+                    matched = {k: res[k] for k in C.TOPIC_MATCH_KEYS}
+                    summary.update(matched)
+                    R.emit(dict(stage=post_stage + "_detail", **matched))
         else:
             R.skip(post_stage)
     except BaseException:

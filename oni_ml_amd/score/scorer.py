@@ -402,6 +402,20 @@ def topic_sides(model, doc: torch.Tensor, word: torch.Tensor):
     return ref(theta.contiguous(), phi.contiguous(), i32(doc), i32(word)), "cpu"
 
 
+def column_l1(A: torch.Tensor, B: torch.Tensor, ia: Optional[torch.Tensor] = None,
+              ib: Optional[torch.Tensor] = None):
+    """``(C float64 [Wa, Wb], path)``: ``C[a, b]`` = the sum over the pairs of ``|A[ia[m], a] - B[ib[m], b]|`` in
+    blocks of ``config.MATCH_BLOCK`` pairs (``ops.hip.column_l1`` on the GPU, its torch twin elsewhere: the same
+    bits).  ``ia`` / ``ib``: int64 rows, both None for the identity.  ``path``: ``"hip"`` or ``"cpu"``."""
+    A, B = A.contiguous(), B.contiguous()
+    i64 = lambda t: None if t is None else t.to(torch.int64).contiguous()      # noqa: E731
+    if A.device.type == "cuda":
+        from ..ops.hip import column_l1 as fn
+        return fn(A, B, i64(ia), i64(ib)), "hip"
+    from ..ops.reference import column_l1 as ref
+    return ref(A, B, i64(ia), i64(ib)), "cpu"
+
+
 def rank_hosts(min_score: torch.Tensor, flagged: torch.Tensor, limit: Optional[int] = None) -> np.ndarray:
     """Document rows with at least one flagged side, ascending by their lowest score, ties to the lowest row
     (int64 host array); ``limit``: only the first ``limit`` of them (the MAXRESULTS radix select and its tie
