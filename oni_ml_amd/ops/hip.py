@@ -275,6 +275,149 @@ def score_events(theta, phi, K, dflt, doc_a, word_a, doc_b, word_b, tol):
 from ..config import ENSEMBLE_MAX    # noqa: E402 -- largest member count; checked against kEnsembleMax at a launch
 
 
+# ------------------------------------------------------- the scoring wrappers' checks ---
+# One definition of every host-side rule of the wrappers below.  None of them reads from the device but
+# ``_in_range`` and ``_segments_in_range``: a wrapper calls those two last, after every other check.
+
+def _max_blocks(max_blocks):
+    if not isinstance(max_blocks, int) or isinstance(max_blocks, bool) or max_blocks < 0:
+        raise ValueError(f"max_blocks must be a non-negative int, got {max_blocks!r}")
+    return max_blocks
+
+
+def _block(who, block, default):
+    """The block size of a wrapper: ``block``, or the ``config`` value when it is None."""
+    import operator
+    B = operator.index(default if block is None else block)
+    if not 1 <= B < 1 << 31:
+        raise ValueError(f"{who}: block must be >= 1 and < 2^31, got {B}")
+    return B
+
+
+def _scratch_mb(who, scratch_mb, default):
+    """The scratch cap of a wrapper in MiB: ``scratch_mb``, or the ``config`` value when it is None."""
+    cap_mb = float(default if scratch_mb is None else scratch_mb)
+    if not cap_mb > 0:
+        raise ValueError(f"{who}: scratch_mb must be > 0, got {scratch_mb!r}")
+    return cap_mb
+
+
+def _scratch_batch(n, per_item, cap_mb, tile=1):
+    """How many of ``n`` items of ``per_item`` scratch bytes run at once under a cap of ``cap_mb`` MiB: at least
+    one, and whole tiles of ``tile`` items where the items need more than one batch of at least a tile."""
+    batch = max(1, min(n, int(cap_mb * (1 << 20)) // per_item))
+    if batch < n and batch >= tile:
+        batch -= batch % tile
+    return batch
+
+
+def _list_scratch_doubles(cells):
+    """The doubles of a top-N list scratch of ``cells`` (value, row) cells: the doubles first, then the ints,
+    rounded up to whole doubles."""
+    return cells + (cells + 1) // 2
+
+
+def _table(name, t, what, dev=None, width=None):
+    """A contiguous float64 GPU table (on ``dev``, when given) of the shape ``what`` names: 2-D, or with
+    ``width`` = (R, K) the 3-D one of that row width."""
+    if not isinstance(t, torch.Tensor) or t.dim() != (2 if width is None else 3):
+        raise ValueError(f"{name}: expected a {what} tensor")
+    if t.dtype != torch.float64:
+        raise ValueError(f"{name}: expected torch.float64, got {t.dtype}")
+    if width is not None and tuple(t.shape[1:]) != width:
+        raise ValueError(f"{name}: row width {tuple(t.shape[1:])} != (R, K) = {width}")
+    if not t.is_cuda:
+        raise ValueError(f"{name}: must be a GPU tensor")
+    if dev is not None and t.device != dev:
+        raise ValueError(f"{name}: on {t.device}, expected {dev}")
+    if not t.is_contiguous():
+        raise ValueError(f"{name}: must be contiguous")
+
+
+def _table3(name, t, R, K, dev=None):
+    _table(name, t, "[rows, R, K]", dev, (R, K))
+
+
+def _members(who, R, K, r_max):
+    """R members x K topics: ``1 <= R <= r_max`` and ``K >= 1``, or with ``r_max`` None both >= 1 and R K < 2^31."""
+    if r_max is None:
+        if R < 1 or K < 1 or R * K >= 1 << 31:
+            raise ValueError(f"{who}: R and K must be >= 1 and R K < 2^31, got {R} x {K}")
+        return
+    if not 1 <= R <= r_max:
+        raise ValueError(f"{who}: R must be in [1, {r_max}], got {R}")
+    if K < 1:
+        raise ValueError(f"{who}: K must be >= 1, got {K}")
+
+
+def _tables3(who, theta, phi=None, r_max=None):
+    """``theta`` [D, R, K] and, when given, ``phi`` [V, R, K] on theta's device: ``(R, K, device)``."""
+    if not isinstance(theta, torch.Tensor) or theta.dim() != 3:
+        raise ValueError("theta: expected a [rows, R, K] tensor")
+    R, K = int(theta.shape[1]), int(theta.shape[2])
+    _members(who, R, K, r_max)
+    _table3("theta", theta, R, K)
+    if phi is not None:
+        _table3("phi", phi, R, K, theta.device)
+    return R, K, theta.device
+
+
+def _vector(name, t, who=None):
+    """``t.numel()`` of a 1-D tensor; with ``who`` (the wrapper) also refused at 2^31 entries or more."""
+    if not isinstance(t, torch.Tensor) or t.dim() != 1:
+        raise ValueError(f"{name}: expected a 1-D tensor")
+    n = t.numel()
+    if who is not None and n >= 1 << 31:
+        raise ValueError(f"{who}: {name} holds {n} entries (< 2^31)")
+    return n
+
+
+def _index(name, t, dtype, shape, dev):
+    if not isinstance(t, torch.Tensor) or t.dtype != dtype:
+        raise ValueError(f"{name}: expected an {str(dtype).replace('torch.', '')} tensor")
+    if t.device != dev:
+        raise ValueError(f"{name}: on {t.device}, expected {dev}")
+    if tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{name}: shape {tuple(t.shape)} != {tuple(shape)}")
+    if not t.is_contiguous():
+        raise ValueError(f"{name}: must be contiguous")
+    return t.data_ptr()
+
+
+def _fields(who, grow):
+    """F of ``grow`` [n, F], the groups of a side's explained fields."""
+    if not isinstance(grow, torch.Tensor) or grow.dim() != 2:
+        raise ValueError("grow: expected an [n, F] tensor")
+    F = int(grow.shape[1])
+    if not 1 <= F <= _CFG.EXPLAIN_MAX_FIELDS:
+        raise ValueError(f"{who}: F must be in [1, {_CFG.EXPLAIN_MAX_FIELDS}], got {F}")
+    return F
+
+
+def _order_segments(order, seg_start, seg_end, dev):
+    """``order`` int32 [n_ord] and ``seg_start`` / ``seg_end`` int64 [G]: ``(G, their three pointers)``."""
+    p_ord = _index("order", order, torch.int32, (_vector("order", order),), dev)
+    G = _vector("seg_start", seg_start)
+    return (G, p_ord, _index("seg_start", seg_start, torch.int64, (G,), dev),
+            _index("seg_end", seg_end, torch.int64, (G,), dev))
+
+
+def _in_range(name, idx, lo, hi):
+    """Two host reads: every entry of ``idx`` in ``[lo, hi)``, before a gather kernel touches memory.  Nothing to
+    read for None or an empty tensor."""
+    if idx is not None and idx.numel() and (int(idx.max()) >= hi or int(idx.min()) < lo):
+        raise ValueError(f"{name}: index out of range")
+
+
+def _segments_in_range(order, V, seg_start, seg_end):
+    """Host reads: ``order`` holds rows of a table of V rows, and 0 <= start <= end <= order.numel()."""
+    _in_range("order", order, 0, V)
+    n_ord = order.numel()
+    if seg_start.numel() and (int(seg_start.min()) < 0 or int((seg_end - seg_start).min()) < 0
+                              or int(seg_end.max()) > n_ord):
+        raise ValueError(f"seg_start / seg_end: segments must satisfy 0 <= start <= end <= {n_ord}")
+
+
 def score_ensemble(theta, phi, R, K, dflt, doc_a, word_a, doc_b, word_b, tol, max_blocks: int = 0):
     """Ensemble scores of R members (csrc/hip/score_ensemble.hip; ``ops.reference.score_ensemble`` is the twin):
     ``(score_a, score_b|None, key, flag, votes)`` as new device tensors.
@@ -286,54 +429,20 @@ def score_ensemble(theta, phi, R, K, dflt, doc_a, word_a, doc_b, word_b, tol, ma
     nothing.  ``max_blocks``: cap on the workgroups (tests: a small cap makes the grid-stride loop wrap)."""
     import operator
     R, K = operator.index(R), operator.index(K)
-    if not isinstance(max_blocks, int) or isinstance(max_blocks, bool) or max_blocks < 0:
-        raise ValueError(f"max_blocks must be a non-negative int, got {max_blocks!r}")
-    if not 1 <= R <= ENSEMBLE_MAX:
-        raise ValueError(f"score_ensemble: R must be in [1, {ENSEMBLE_MAX}], got {R}")
-    if K < 1:
-        raise ValueError(f"score_ensemble: K must be >= 1, got {K}")
-    for name, t in (("theta", theta), ("phi", phi)):
-        if not isinstance(t, torch.Tensor) or t.dim() != 3:
-            raise ValueError(f"{name}: expected a [rows, R, K] tensor")
-        if t.dtype != torch.float64:
-            raise ValueError(f"{name}: expected torch.float64, got {t.dtype}")
-        if tuple(t.shape[1:]) != (R, K):
-            raise ValueError(f"{name}: row width {tuple(t.shape[1:])} != (R, K) = {(R, K)}")
-        if not t.is_cuda:
-            raise ValueError(f"{name}: must be a GPU tensor")
-        if not t.is_contiguous():
-            raise ValueError(f"{name}: must be contiguous")
-    if phi.device != theta.device:
-        raise ValueError(f"phi: on {phi.device}, expected {theta.device} (theta's device)")
+    _max_blocks(max_blocks)
+    _members("score_ensemble", R, K, ENSEMBLE_MAX)
+    _table3("theta", theta, R, K)
+    dev = theta.device
+    _table3("phi", phi, R, K, dev)
     if (doc_b is None) != (word_b is None):
         raise ValueError("score_ensemble: doc_b and word_b go together")
-    if not isinstance(doc_a, torch.Tensor) or doc_a.dim() != 1:
-        raise ValueError("doc_a: expected a 1-D tensor")
-    dev = theta.device
-    D, V = theta.shape[0], phi.shape[0]
-    n = doc_a.numel()
-    if n >= 1 << 31:
-        raise ValueError(f"score_ensemble: {n} events (n < 2^31)")
+    n = _vector("doc_a", doc_a, "score_ensemble")
     two = doc_b is not None
-    ptr = []
-    for name, idx in (("doc_a", doc_a), ("word_a", word_a), ("doc_b", doc_b), ("word_b", word_b)):
-        if idx is None:
-            ptr.append(0)
-            continue
-        if not isinstance(idx, torch.Tensor) or idx.dtype != torch.int32:
-            raise ValueError(f"{name}: expected an int32 tensor")
-        if idx.device != dev:
-            raise ValueError(f"{name}: on {idx.device}, expected {dev}")
-        if tuple(idx.shape) != (n,):
-            raise ValueError(f"{name}: shape {tuple(idx.shape)} != {(n,)}")
-        if not idx.is_contiguous():
-            raise ValueError(f"{name}: must be contiguous")
-        ptr.append(idx.data_ptr())
-    # index bounds (host check before a gather kernel touches memory)
-    if n:
-        for name, idx, lim in (("doc_a", doc_a, D), ("word_a", word_a, V), ("doc_b", doc_b, D), ("word_b", word_b, V)):
-            if idx is not None and (int(idx.max()) >= lim or int(idx.min()) < -1):
-                raise ValueError(f"{name}: index out of range")
+    sides = (("doc_a", doc_a, theta.shape[0]), ("word_a", word_a, phi.shape[0]),
+             ("doc_b", doc_b, theta.shape[0]), ("word_b", word_b, phi.shape[0]))
+    ptr = [0 if idx is None else _index(name, idx, torch.int32, (n,), dev) for name, idx, _ in sides]
+    for name, idx, rows in sides:
+        _in_range(name, idx, -1, rows)
     sa = torch.empty(n, dtype=torch.float64, device=dev)
     sb = torch.empty(n, dtype=torch.float64, device=dev) if two else None
     key = torch.empty(n, dtype=torch.float64, device=dev)
@@ -363,14 +472,9 @@ def select_lowest(key, flag, limit, max_blocks: int = 0, with_count: bool = Fals
     limit = operator.index(limit)      # TypeError for a float
     if limit < 1:
         raise ValueError(f"limit must be >= 1, got {limit}")
-    if not isinstance(max_blocks, int) or max_blocks < 0:
-        raise ValueError(f"max_blocks must be a non-negative int, got {max_blocks!r}")
-    if not isinstance(key, torch.Tensor) or key.dim() != 1:
-        raise ValueError("key: expected a 1-D tensor")
-    n = key.numel()
+    _max_blocks(max_blocks)
+    n = _vector("key", key, "select_lowest")      # the kernels count in 32 bits
     dev = key.device
-    if n >= 1 << 31:
-        raise ValueError(f"select_lowest: {n} rows, the kernels count in 32 bits (n < 2^31)")
     p_key = _chk(key, torch.float64, "key", (n,), dev)
     p_flag = _chk(flag, torch.uint8, "flag", (n,), dev)
     if n == 0:
@@ -408,29 +512,21 @@ def host_summary(doc_a, score_a, doc_b, score_b, num_docs, tol, max_blocks: int 
     on it.  ``stats``: also return, as a sixth value, the atomics issued ``(counts, min_key, worst)``
     (measurement: scripts/host_report_bench.py)."""
     import operator
-    if not isinstance(max_blocks, int) or isinstance(max_blocks, bool) or max_blocks < 0:
-        raise ValueError(f"max_blocks must be a non-negative int, got {max_blocks!r}")
+    _max_blocks(max_blocks)
     D = operator.index(num_docs)
     if D < 0 or D >= 1 << 31:
         raise ValueError(f"num_docs must be in [0, 2^31), got {D}")
     if (doc_b is None) != (score_b is None):
         raise ValueError("host_summary: doc_b and score_b go together")
-    if not isinstance(doc_a, torch.Tensor) or doc_a.dim() != 1:
-        raise ValueError("doc_a: expected a 1-D tensor")
-    n = doc_a.numel()
+    n = _vector("doc_a", doc_a, "host_summary")      # side numbers are 32-bit
     dev = doc_a.device
-    if n >= 1 << 31:
-        raise ValueError(f"host_summary: {n} events, side numbers are 32-bit (n < 2^31)")
     two = doc_b is not None
     ptr = [_chk(doc_a, torch.int32, "doc_a", (n,), dev), _chk(score_a, torch.float64, "score_a", (n,), dev),
            _chk(doc_b, torch.int32, "doc_b", (n,), dev) if two else 0,
            _chk(score_b, torch.float64, "score_b", (n,), dev) if two else 0]
     L = lib()
-    # index bounds (host check before the scatter kernel touches memory)
-    if n:
-        for name, idx in (("doc_a", doc_a), ("doc_b", doc_b)):
-            if idx is not None and (int(idx.max()) >= D or int(idx.min()) < -1):
-                raise ValueError(f"{name}: index out of range")
+    _in_range("doc_a", doc_a, -1, D)
+    _in_range("doc_b", doc_b, -1, D)
     sides = n * (2 if two else 1)
     if n == 0 or D == 0:      # nothing to fold: every side (D == 0: all at -1, checked above) is skipped
         out = (torch.zeros(D, dtype=torch.int64, device=dev), torch.zeros(D, dtype=torch.int64, device=dev),
@@ -457,39 +553,6 @@ def host_summary(doc_a, score_a, doc_b, score_b, num_docs, tol, max_blocks: int 
     return out + (tuple(host[1:]),) if stats else out
 
 
-def _max_blocks(max_blocks):
-    if not isinstance(max_blocks, int) or isinstance(max_blocks, bool) or max_blocks < 0:
-        raise ValueError(f"max_blocks must be a non-negative int, got {max_blocks!r}")
-    return max_blocks
-
-
-def _table3(name, t, R, K, dev=None):
-    if not isinstance(t, torch.Tensor) or t.dim() != 3:
-        raise ValueError(f"{name}: expected a [rows, R, K] tensor")
-    if t.dtype != torch.float64:
-        raise ValueError(f"{name}: expected torch.float64, got {t.dtype}")
-    if tuple(t.shape[1:]) != (R, K):
-        raise ValueError(f"{name}: row width {tuple(t.shape[1:])} != (R, K) = {(R, K)}")
-    if not t.is_cuda:
-        raise ValueError(f"{name}: must be a GPU tensor")
-    if dev is not None and t.device != dev:
-        raise ValueError(f"{name}: on {t.device}, expected {dev}")
-    if not t.is_contiguous():
-        raise ValueError(f"{name}: must be contiguous")
-
-
-def _index(name, t, dtype, shape, dev):
-    if not isinstance(t, torch.Tensor) or t.dtype != dtype:
-        raise ValueError(f"{name}: expected an {str(dtype).replace('torch.', '')} tensor")
-    if t.device != dev:
-        raise ValueError(f"{name}: on {t.device}, expected {dev}")
-    if tuple(t.shape) != tuple(shape):
-        raise ValueError(f"{name}: shape {tuple(t.shape)} != {tuple(shape)}")
-    if not t.is_contiguous():
-        raise ValueError(f"{name}: must be contiguous")
-    return t.data_ptr()
-
-
 def group_rows_sum(table, order, seg_start, seg_end, max_blocks: int = 0, block=None):
     """Sums of table rows over segments of a row order (csrc/hip/explain.hip; ``ops.reference.group_rows_sum`` is
     the twin): float64 [G, W], row g the sum of ``table[order[seg_start[g] : seg_end[g]]]``, column by column.
@@ -501,42 +564,20 @@ def group_rows_sum(table, order, seg_start, seg_end, max_blocks: int = 0, block=
     on the host before the launch (host reads: the bounds of ``order`` and of the segments, the block count);
     ``G == 0`` launches nothing.  ``max_blocks``: cap on the workgroups per launch (tests: a small cap makes the
     grid-stride loops wrap).  ``block``: another block size (measurement: scripts/explain_bench.py)."""
-    import operator
     _max_blocks(max_blocks)
-    GB = operator.index(_CFG.GROUP_BLOCK if block is None else block)
-    if GB < 1:
-        raise ValueError(f"group_rows_sum: block must be >= 1, got {GB}")
-    if not isinstance(table, torch.Tensor) or table.dim() != 2:
-        raise ValueError("table: expected a [V, W] tensor")
-    if table.dtype != torch.float64:
-        raise ValueError(f"table: expected torch.float64, got {table.dtype}")
-    if not table.is_cuda:
-        raise ValueError("table: must be a GPU tensor")
-    if not table.is_contiguous():
-        raise ValueError("table: must be contiguous")
+    GB = _block("group_rows_sum", block, _CFG.GROUP_BLOCK)
+    _table("table", table, "[V, W]")
     dev = table.device
     V, W = table.shape
     if W < 1 or V >= 1 << 31:
         raise ValueError(f"table: shape {tuple(table.shape)} (W >= 1, V < 2^31)")
-    if not isinstance(order, torch.Tensor) or order.dim() != 1:
-        raise ValueError("order: expected a 1-D tensor")
-    n_ord = order.numel()
-    p_ord = _index("order", order, torch.int32, (n_ord,), dev)
-    if not isinstance(seg_start, torch.Tensor) or seg_start.dim() != 1:
-        raise ValueError("seg_start: expected a 1-D tensor")
-    G = seg_start.numel()
+    G, p_ord, p_s, p_e = _order_segments(order, seg_start, seg_end, dev)
     if G >= 1 << 31:
         raise ValueError(f"group_rows_sum: {G} segments (G < 2^31)")
-    p_s = _index("seg_start", seg_start, torch.int64, (G,), dev)
-    p_e = _index("seg_end", seg_end, torch.int64, (G,), dev)
     out = torch.empty((G, W), dtype=torch.float64, device=dev)
     if G == 0:
         return out
-    # bounds (host checks before a gather kernel touches memory)
-    if n_ord and (int(order.min()) < 0 or int(order.max()) >= V):
-        raise ValueError("order: index out of range")
-    if int(seg_start.min()) < 0 or int((seg_end - seg_start).min()) < 0 or int(seg_end.max()) > n_ord:
-        raise ValueError(f"seg_start / seg_end: segments must satisfy 0 <= start <= end <= {n_ord}")
+    _segments_in_range(order, V, seg_start, seg_end)
     blk_off = torch.zeros(G + 1, dtype=torch.int64, device=dev)
     blk_off[1:] = torch.cumsum((seg_end - seg_start + (GB - 1)) // GB, 0)
     B = int(blk_off[-1])
@@ -559,36 +600,16 @@ def explain_sides(theta, phi, gsum, doc, word, grow, dflt, max_blocks: int = 0):
     where ``word[i] < 0`` or ``grow[i, f] < 0``; ``why[i]`` the lowest f with the lowest non-NaN cond, 255 when
     there is none.  Everything is checked on the host before the launch; ``n == 0`` launches nothing."""
     _max_blocks(max_blocks)
-    if not isinstance(theta, torch.Tensor) or theta.dim() != 3:
-        raise ValueError("theta: expected a [rows, R, K] tensor")
-    R, K = int(theta.shape[1]), int(theta.shape[2])
-    if not 1 <= R <= ENSEMBLE_MAX:
-        raise ValueError(f"explain_sides: R must be in [1, {ENSEMBLE_MAX}], got {R}")
-    if K < 1:
-        raise ValueError(f"explain_sides: K must be >= 1, got {K}")
-    _table3("theta", theta, R, K)
-    dev = theta.device
-    _table3("phi", phi, R, K, dev)
+    R, K, dev = _tables3("explain_sides", theta, phi, ENSEMBLE_MAX)
     _table3("gsum", gsum, R, K, dev)
-    if not isinstance(doc, torch.Tensor) or doc.dim() != 1:
-        raise ValueError("doc: expected a 1-D tensor")
-    n = doc.numel()
-    if n >= 1 << 31:
-        raise ValueError(f"explain_sides: {n} sides (n < 2^31)")
-    if not isinstance(grow, torch.Tensor) or grow.dim() != 2:
-        raise ValueError("grow: expected an [n, F] tensor")
-    F = int(grow.shape[1])
-    if not 1 <= F <= _CFG.EXPLAIN_MAX_FIELDS:
-        raise ValueError(f"explain_sides: F must be in [1, {_CFG.EXPLAIN_MAX_FIELDS}], got {F}")
+    n = _vector("doc", doc, "explain_sides")
+    F = _fields("explain_sides", grow)
     p_doc = _index("doc", doc, torch.int32, (n,), dev)
     p_word = _index("word", word, torch.int32, (n,), dev)
     p_grow = _index("grow", grow, torch.int32, (n, F), dev)
-    # index bounds (host check before a gather kernel touches memory)
-    if n:
-        for name, idx, lim in (("doc", doc, theta.shape[0]), ("word", word, phi.shape[0]),
-                               ("grow", grow, gsum.shape[0])):
-            if int(idx.max()) >= lim or int(idx.min()) < -1:
-                raise ValueError(f"{name}: index out of range")
+    _in_range("doc", doc, -1, theta.shape[0])
+    _in_range("word", word, -1, phi.shape[0])
+    _in_range("grow", grow, -1, gsum.shape[0])
     cond = torch.empty((n, F), dtype=torch.float64, device=dev)
     why = torch.empty(n, dtype=torch.uint8, device=dev)
     if n == 0:
@@ -634,45 +655,18 @@ def expect_sides(theta, phi, order, seg_start, seg_end, doc, word, grow, dflt, m
     ``max_blocks``: cap on the workgroups per launch (tests: a small cap makes the grid-stride loops wrap).
     ``block``: another block size (measurement: scripts/expect_bench.py).  ``form``: one of ``EXPECT_FORMS`` (None:
     the default)."""
-    import operator
-
     from . import sortgroup as SG
     _max_blocks(max_blocks)
     if form is not None and form not in EXPECT_FORMS:
         raise ValueError(f"expect_sides: form must be one of {EXPECT_FORMS}, got {form!r}")
-    GB = operator.index(_CFG.GROUP_BLOCK if block is None else block)
-    if not 1 <= GB < 1 << 31:
-        raise ValueError(f"expect_sides: block must be in [1, 2^31), got {GB}")
-    if not isinstance(theta, torch.Tensor) or theta.dim() != 3:
-        raise ValueError("theta: expected a [rows, R, K] tensor")
-    R, K = int(theta.shape[1]), int(theta.shape[2])
-    if not 1 <= R <= ENSEMBLE_MAX:
-        raise ValueError(f"expect_sides: R must be in [1, {ENSEMBLE_MAX}], got {R}")
-    if K < 1:
-        raise ValueError(f"expect_sides: K must be >= 1, got {K}")
-    _table3("theta", theta, R, K)
-    dev = theta.device
-    _table3("phi", phi, R, K, dev)
+    GB = _block("expect_sides", block, _CFG.GROUP_BLOCK)
+    R, K, dev = _tables3("expect_sides", theta, phi, ENSEMBLE_MAX)
     V = int(phi.shape[0])
     if V >= 1 << 31:
         raise ValueError(f"expect_sides: {V} phi rows (V < 2^31)")
-    if not isinstance(order, torch.Tensor) or order.dim() != 1:
-        raise ValueError("order: expected a 1-D tensor")
-    n_ord = order.numel()
-    p_ord = _index("order", order, torch.int32, (n_ord,), dev)
-    if not isinstance(seg_start, torch.Tensor) or seg_start.dim() != 1:
-        raise ValueError("seg_start: expected a 1-D tensor")
-    G = seg_start.numel()
-    _index("seg_start", seg_start, torch.int64, (G,), dev)
-    _index("seg_end", seg_end, torch.int64, (G,), dev)
-    if not isinstance(doc, torch.Tensor) or doc.dim() != 1:
-        raise ValueError("doc: expected a 1-D tensor")
-    n = doc.numel()
-    if not isinstance(grow, torch.Tensor) or grow.dim() != 2:
-        raise ValueError("grow: expected an [n, F] tensor")
-    F = int(grow.shape[1])
-    if not 1 <= F <= _CFG.EXPLAIN_MAX_FIELDS:
-        raise ValueError(f"expect_sides: F must be in [1, {_CFG.EXPLAIN_MAX_FIELDS}], got {F}")
+    G, p_ord, _, _ = _order_segments(order, seg_start, seg_end, dev)
+    n = _vector("doc", doc)
+    F = _fields("expect_sides", grow)
     M = n * F
     if M >= 1 << 31:
         raise ValueError(f"expect_sides: {n} pairs x {F} fields (n F < 2^31)")
@@ -684,14 +678,10 @@ def expect_sides(theta, phi, order, seg_start, seg_end, doc, word, grow, dflt, m
     above = torch.empty((n, F), dtype=torch.int32, device=dev)
     if n == 0:
         return best, pbest, above
-    # bounds (host checks before a gather kernel touches memory)
-    for name, idx, lim in (("doc", doc, theta.shape[0]), ("word", word, V), ("grow", grow, G)):
-        if int(idx.max()) >= lim or int(idx.min()) < -1:
-            raise ValueError(f"{name}: index out of range")
-    if n_ord and (int(order.min()) < 0 or int(order.max()) >= V):
-        raise ValueError("order: index out of range")
-    if G and (int(seg_start.min()) < 0 or int((seg_end - seg_start).min()) < 0 or int(seg_end.max()) > n_ord):
-        raise ValueError(f"seg_start / seg_end: segments must satisfy 0 <= start <= end <= {n_ord}")
+    _in_range("doc", doc, -1, theta.shape[0])
+    _in_range("word", word, -1, V)
+    _in_range("grow", grow, -1, G)
+    _segments_in_range(order, V, seg_start, seg_end)
     L = lib()
     if L.ensemble_max() != ENSEMBLE_MAX or L.explain_max_fields() != _CFG.EXPLAIN_MAX_FIELDS:
         raise RuntimeError("expect_sides: config.ENSEMBLE_MAX / EXPLAIN_MAX_FIELDS differ from the compiled limits")
@@ -773,32 +763,14 @@ def tail_mass_docs(theta, phi, doc, word, block=None, max_blocks: int = 0, scrat
 
 def _tail_launch(who, docs, theta, phi, doc, word, block, max_blocks, scratch_mb):
     """The checks, the scratch batches and the launches of ``tail_mass`` and (``docs``) ``tail_mass_docs``."""
-    import operator
     _max_blocks(max_blocks)
-    TB = operator.index(_CFG.TAIL_BLOCK if block is None else block)
-    if TB < 1:
-        raise ValueError(f"{who}: block must be >= 1, got {TB}")
-    cap_mb = float(_CFG.TAIL_SCRATCH_MB if scratch_mb is None else scratch_mb)
-    if not cap_mb > 0:
-        raise ValueError(f"{who}: scratch_mb must be > 0, got {scratch_mb!r}")
-    if not isinstance(theta, torch.Tensor) or theta.dim() != 3:
-        raise ValueError("theta: expected a [rows, R, K] tensor")
-    R, K = int(theta.shape[1]), int(theta.shape[2])
-    if not 1 <= R <= ENSEMBLE_MAX:
-        raise ValueError(f"{who}: R must be in [1, {ENSEMBLE_MAX}], got {R}")
-    if K < 1:
-        raise ValueError(f"{who}: K must be >= 1, got {K}")
-    _table3("theta", theta, R, K)
-    dev = theta.device
-    _table3("phi", phi, R, K, dev)
+    TB = _block(who, block, _CFG.TAIL_BLOCK)
+    cap_mb = _scratch_mb(who, scratch_mb, _CFG.TAIL_SCRATCH_MB)
+    R, K, dev = _tables3(who, theta, phi, ENSEMBLE_MAX)
     V = int(phi.shape[0])
-    if V >= 1 << 31 or TB >= 1 << 31:
-        raise ValueError(f"{who}: {V} phi rows, block {TB} (both < 2^31)")
-    if not isinstance(doc, torch.Tensor) or doc.dim() != 1:
-        raise ValueError("doc: expected a 1-D tensor")
-    n = doc.numel()
-    if n >= 1 << 31:
-        raise ValueError(f"{who}: {n} sides (n < 2^31)")
+    if V >= 1 << 31:
+        raise ValueError(f"{who}: {V} phi rows (V < 2^31)")
+    n = _vector("doc", doc, who)
     _index("doc", doc, torch.int32, (n,), dev)
     _index("word", word, torch.int32, (n,), dev)
     le = torch.empty(n, dtype=torch.float64, device=dev)
@@ -807,10 +779,8 @@ def _tail_launch(who, docs, theta, phi, doc, word, block, max_blocks, scratch_mb
     ties = torch.empty(n, dtype=torch.int32, device=dev)
     if n == 0:
         return le, tot, rarer, ties
-    # index bounds (host check before a gather kernel touches memory)
-    for name, idx, lim in (("doc", doc, theta.shape[0]), ("word", word, V)):
-        if int(idx.max()) >= lim or int(idx.min()) < (0 if docs else -1):
-            raise ValueError(f"{name}: index out of range")
+    _in_range("doc", doc, 0 if docs else -1, theta.shape[0])
+    _in_range("word", word, 0 if docs else -1, V)
     if docs and n > 1 and bool((doc[1:] < doc[:-1]).any()):
         raise ValueError(f"{who}: doc must be non-decreasing (the pairs sorted by document)")
     L = lib()
@@ -821,10 +791,7 @@ def _tail_launch(who, docs, theta, phi, doc, word, block, max_blocks, scratch_mb
     if L.ensemble_max() != ENSEMBLE_MAX:
         raise RuntimeError(f"{who}: config.ENSEMBLE_MAX differs from the compiled limit")
     nblk = -(-V // TB)
-    per_side = 24 * max(nblk, 1)
-    batch = max(1, min(n, int(cap_mb * (1 << 20)) // per_side))
-    if batch < n and batch >= 256:
-        batch -= batch % 256      # whole tiles of sides
+    batch = _scratch_batch(n, 24 * max(nblk, 1), cap_mb, 256)      # whole tiles of sides
     scratch = torch.empty(batch * max(nblk, 1) * 3, dtype=torch.float64, device=dev)
     for s0 in range(0, n, batch):
         m = min(batch, n - s0)
@@ -859,48 +826,30 @@ def peer_topn(theta3, query, n, block=None, max_blocks: int = 0, scratch_mb=None
     small cap makes the grid-stride loops wrap)."""
     import operator
     _max_blocks(max_blocks)
-    PB = operator.index(_CFG.PEERS_BLOCK if block is None else block)
-    if PB < 1:
-        raise ValueError(f"peer_topn: block must be >= 1, got {PB}")
-    cap_mb = float(_CFG.PEERS_SCRATCH_MB if scratch_mb is None else scratch_mb)
-    if not cap_mb > 0:
-        raise ValueError(f"peer_topn: scratch_mb must be > 0, got {scratch_mb!r}")
+    PB = _block("peer_topn", block, _CFG.PEERS_BLOCK)
+    cap_mb = _scratch_mb("peer_topn", scratch_mb, _CFG.PEERS_SCRATCH_MB)
     N = operator.index(n)
     if not 1 <= N <= _CFG.PEERS_MAX:
         raise ValueError(f"peer_topn: n must be in [1, {_CFG.PEERS_MAX}], got {N}")
-    if not isinstance(theta3, torch.Tensor) or theta3.dim() != 3:
-        raise ValueError("theta: expected a [rows, R, K] tensor")
-    D, R, K = (int(x) for x in theta3.shape)
-    if R < 1 or K < 1 or R * K >= 1 << 31:
-        raise ValueError(f"peer_topn: R and K must be >= 1 and R K < 2^31, got {R} x {K}")
-    _table3("theta", theta3, R, K)
-    dev = theta3.device
-    if D >= 1 << 31 or PB >= 1 << 31:
-        raise ValueError(f"peer_topn: {D} theta rows, block {PB} (both < 2^31)")
-    if not isinstance(query, torch.Tensor) or query.dim() != 1:
-        raise ValueError("query: expected a 1-D tensor")
-    Q = query.numel()
-    if Q >= 1 << 31:
-        raise ValueError(f"peer_topn: {Q} queries (Q < 2^31)")
+    R, K, dev = _tables3("peer_topn", theta3)
+    D = int(theta3.shape[0])
+    if D >= 1 << 31:
+        raise ValueError(f"peer_topn: {D} theta rows (D < 2^31)")
+    Q = _vector("query", query, "peer_topn")
     _index("query", query, torch.int32, (Q,), dev)
     rows = torch.empty((Q, N), dtype=torch.int32, device=dev)
     dist = torch.empty((Q, N), dtype=torch.float64, device=dev)
     count = torch.empty(Q, dtype=torch.int32, device=dev)
     if Q == 0:
         return rows, dist, count
-    # index bounds (host check before a kernel touches memory)
-    if int(query.max()) >= D or int(query.min()) < 0:
-        raise ValueError("query: index out of range")
+    _in_range("query", query, 0, D)
     L = lib()
     if L.peers_max() != _CFG.PEERS_MAX:
         raise RuntimeError("peer_topn: config.PEERS_MAX differs from the compiled limit")
     nblk = -(-D // PB)
-    per_query = 12 * N * nblk
-    batch = max(1, min(Q, int(cap_mb * (1 << 20)) // per_query))
-    if batch < Q and batch >= 256:
-        batch -= batch % 256      # whole tiles of queries
-    # doubles first, then ints: [nblk][N][batch] of each, rounded up to whole doubles
-    scratch = torch.empty(batch * nblk * N + (batch * nblk * N + 1) // 2, dtype=torch.float64, device=dev)
+    batch = _scratch_batch(Q, 12 * N * nblk, cap_mb, 256)      # whole tiles of queries
+    # [nblk][N][batch] doubles, then as many ints
+    scratch = torch.empty(_list_scratch_doubles(batch * nblk * N), dtype=torch.float64, device=dev)
     for s0 in range(0, Q, batch):
         m = min(batch, Q - s0)
         L.peer_topn(theta3.data_ptr(), R * K, D, query.data_ptr() + 4 * s0, int(m), N, int(PB), int(nblk),
@@ -938,26 +887,15 @@ def column_topn(table, n, block=None, max_blocks: int = 0, scratch_mb=None, samp
     compare per load.  A bound from a subset of the rows excludes nothing that is listed: the same bits."""
     import operator
     _max_blocks(max_blocks)
-    TB = operator.index(_CFG.TOPIC_BLOCK if block is None else block)
-    if TB < 1 or TB >= 1 << 31:
-        raise ValueError(f"column_topn: block must be in [1, 2^31), got {TB}")
+    TB = _block("column_topn", block, _CFG.TOPIC_BLOCK)
     S = operator.index(_CFG.TOPIC_SAMPLE if sample is None else sample)
     if S < 1:
         raise ValueError(f"column_topn: sample must be >= 1, got {S}")
-    cap_mb = float(_CFG.TOPIC_SCRATCH_MB if scratch_mb is None else scratch_mb)
-    if not cap_mb > 0:
-        raise ValueError(f"column_topn: scratch_mb must be > 0, got {scratch_mb!r}")
+    cap_mb = _scratch_mb("column_topn", scratch_mb, _CFG.TOPIC_SCRATCH_MB)
     N = operator.index(n)
     if not 1 <= N <= _CFG.TOPIC_REPORT_MAX:
         raise ValueError(f"column_topn: n must be in [1, {_CFG.TOPIC_REPORT_MAX}], got {N}")
-    if not isinstance(table, torch.Tensor) or table.dim() != 2:
-        raise ValueError("table: expected a [rows, W] tensor")
-    if table.dtype != torch.float64:
-        raise ValueError(f"table: expected torch.float64, got {table.dtype}")
-    if not table.is_cuda:
-        raise ValueError("table: must be a GPU tensor")
-    if not table.is_contiguous():
-        raise ValueError("table: must be contiguous")
+    _table("table", table, "[rows, W]")
     dev = table.device
     D, W = (int(x) for x in table.shape)
     if D > (1 << 31) - 65536 or W >= 1 << 31:
@@ -977,17 +915,13 @@ def column_topn(table, n, block=None, max_blocks: int = 0, scratch_mb=None, samp
     s_rows_n = (D - 1) // stride + 1 if stride else 0
     s_block = min(TB, 256)
     s_nblk = -(-s_rows_n // s_block)
-    per_col = 12 * N * max(nblk, s_nblk)
-    batch = max(1, min(W, int(cap_mb * (1 << 20)) // per_col))
-    T = L.topic_threads(N)
-    if batch < W and batch >= T:
-        batch -= batch % T      # whole tiles of columns
-    # doubles first, then ints: [nblk][N][batch] of each, rounded up to whole doubles
-    cells = batch * max(nblk, s_nblk) * N
-    scratch = torch.empty(cells + (cells + 1) // 2, dtype=torch.float64, device=dev)
+    # whole tiles of columns
+    batch = _scratch_batch(W, 12 * N * max(nblk, s_nblk), cap_mb, L.topic_threads(N))
+    # [nblk][N][batch] doubles, then as many ints
+    scratch = torch.empty(_list_scratch_doubles(batch * max(nblk, s_nblk) * N), dtype=torch.float64, device=dev)
     # pass 2 in two levels where the blocks are many: the lists of the groups of blocks
     cells2 = batch * max(L.topic_merge_groups(nblk), L.topic_merge_groups(s_nblk)) * N
-    scratch2 = torch.empty(cells2 + (cells2 + 1) // 2, dtype=torch.float64, device=dev) if cells2 else None
+    scratch2 = torch.empty(_list_scratch_doubles(cells2), dtype=torch.float64, device=dev) if cells2 else None
     p2 = scratch2.data_ptr() if cells2 else 0
     if stride:
         s_out = (torch.empty((W, N), dtype=torch.int32, device=dev),
@@ -1042,20 +976,8 @@ def topic_sides(theta3, phi3, doc, word, max_blocks: int = 0):
     member.  A side without a θ row or a φ row, or with NaN products only: -1, NaN, NaN, -1.  Every index is checked
     on the host before the launch; no side launches nothing."""
     _max_blocks(max_blocks)
-    if not isinstance(theta3, torch.Tensor) or theta3.dim() != 3:
-        raise ValueError("theta: expected a [rows, R, K] tensor")
-    D, R, K = (int(x) for x in theta3.shape)
-    if R < 1 or K < 1 or R * K >= 1 << 31:
-        raise ValueError(f"topic_sides: R and K must be >= 1 and R K < 2^31, got {R} x {K}")
-    _table3("theta", theta3, R, K)
-    dev = theta3.device
-    _table3("phi", phi3, R, K, dev)
-    V = int(phi3.shape[0])
-    if not isinstance(doc, torch.Tensor) or doc.dim() != 1:
-        raise ValueError("doc: expected a 1-D tensor")
-    n = doc.numel()
-    if n >= 1 << 31:
-        raise ValueError(f"topic_sides: {n} sides (n < 2^31)")
+    R, K, dev = _tables3("topic_sides", theta3, phi3)
+    n = _vector("doc", doc, "topic_sides")
     _index("doc", doc, torch.int32, (n,), dev)
     _index("word", word, torch.int32, (n,), dev)
     col = torch.empty(n, dtype=torch.int32, device=dev)
@@ -1064,11 +986,8 @@ def topic_sides(theta3, phi3, doc, word, max_blocks: int = 0):
     ht = torch.empty(n, dtype=torch.int32, device=dev)
     if n == 0:
         return col, resp, share, ht
-    # index bounds (host check before a gather kernel touches memory)
-    if int(doc.max()) >= D or int(doc.min()) < -1:
-        raise ValueError("doc: index out of range")
-    if int(word.max()) >= V or int(word.min()) < -1:
-        raise ValueError("word: index out of range")
+    _in_range("doc", doc, -1, theta3.shape[0])
+    _in_range("word", word, -1, phi3.shape[0])
     lib().topic_sides(theta3.data_ptr(), phi3.data_ptr(), R, K, doc.data_ptr(), word.data_ptr(), n, col.data_ptr(),
                       resp.data_ptr(), share.data_ptr(), ht.data_ptr(), int(max_blocks), _stream())
     return col, resp, share, ht
@@ -1097,26 +1016,12 @@ def column_l1(A, B, ia=None, ib=None, block=None, max_blocks: int = 0, scratch_m
     before -- the same sequence of adds.  Everything is checked on the host before a launch (host reads: the bounds
     of the indices); ``M == 0`` launches nothing.  ``max_blocks``: cap on the workgroups per launch (tests: a small
     cap makes the grid-stride loops wrap)."""
-    import operator
     _max_blocks(max_blocks)
-    MB = operator.index(_CFG.MATCH_BLOCK if block is None else block)
-    if MB < 1 or MB >= 1 << 31:
-        raise ValueError(f"column_l1: block must be in [1, 2^31), got {MB}")
-    cap_mb = float(_CFG.MATCH_SCRATCH_MB if scratch_mb is None else scratch_mb)
-    if not cap_mb > 0:
-        raise ValueError(f"column_l1: scratch_mb must be > 0, got {scratch_mb!r}")
-    for name, t in (("A", A), ("B", B)):
-        if not isinstance(t, torch.Tensor) or t.dim() != 2:
-            raise ValueError(f"{name}: expected a [rows, W] tensor")
-        if t.dtype != torch.float64:
-            raise ValueError(f"{name}: expected torch.float64, got {t.dtype}")
-        if not t.is_cuda:
-            raise ValueError(f"{name}: must be a GPU tensor")
-        if not t.is_contiguous():
-            raise ValueError(f"{name}: must be contiguous")
+    MB = _block("column_l1", block, _CFG.MATCH_BLOCK)
+    cap_mb = _scratch_mb("column_l1", scratch_mb, _CFG.MATCH_SCRATCH_MB)
+    _table("A", A, "[rows, W]")
     dev = A.device
-    if B.device != dev:
-        raise ValueError(f"B: on {B.device}, expected {dev}")
+    _table("B", B, "[rows, W]", dev)
     (Va, Wa), (Vb, Wb) = (int(x) for x in A.shape), (int(x) for x in B.shape)
     if (ia is None) != (ib is None):
         raise ValueError("column_l1: ia and ib go together (both None: the identity)")
@@ -1125,12 +1030,8 @@ def column_l1(A, B, ia=None, ib=None, block=None, max_blocks: int = 0, scratch_m
             raise ValueError(f"column_l1: the identity form needs tables of equal height, got {Va} and {Vb}")
         M, p_ia, p_ib = Va, 0, 0
     else:
-        if not isinstance(ia, torch.Tensor) or ia.dim() != 1:
-            raise ValueError("ia: expected a 1-D tensor")
-        if not isinstance(ib, torch.Tensor) or ib.dim() != 1:
-            raise ValueError("ib: expected a 1-D tensor")
-        M = ia.numel()
-        if ib.numel() != M:
+        M = _vector("ia", ia)
+        if _vector("ib", ib) != M:
             raise ValueError(f"column_l1: ia has {M} rows, ib {ib.numel()}")
         p_ia = _index("ia", ia, torch.int64, (M,), dev)
         p_ib = _index("ib", ib, torch.int64, (M,), dev)
@@ -1140,14 +1041,10 @@ def column_l1(A, B, ia=None, ib=None, block=None, max_blocks: int = 0, scratch_m
     out = torch.zeros((Wa, Wb), dtype=torch.float64, device=dev)
     if M == 0 or Wa == 0 or Wb == 0:
         return out
-    # index bounds (host check before a gather kernel touches memory)
-    if ia is not None:
-        if int(ia.min()) < 0 or int(ia.max()) >= Va:
-            raise ValueError("ia: index out of range")
-        if int(ib.min()) < 0 or int(ib.max()) >= Vb:
-            raise ValueError("ib: index out of range")
+    _in_range("ia", ia, 0, Va)
+    _in_range("ib", ib, 0, Vb)
     nblk = -(-M // MB)
-    batch = max(1, min(nblk, int(cap_mb * (1 << 20)) // (8 * Wa * Wb)))
+    batch = _scratch_batch(nblk, 8 * Wa * Wb, cap_mb)
     scratch = torch.empty(batch * Wa * Wb, dtype=torch.float64, device=dev)
     for b0 in range(0, nblk, batch):
         L.column_l1(A.data_ptr(), B.data_ptr(), Va, Vb, Wa, Wb, p_ia, p_ib, int(M), int(MB), int(b0),
@@ -1208,35 +1105,19 @@ def holdout_entries(theta, phi, doc, word, t, word_seen, max_blocks: int = 0):
     natural log of correctly rounded fp64 operations in a fixed order.  Everything is checked on the host before
     the launch; ``n == 0`` launches nothing."""
     _max_blocks(max_blocks)
-    for name, x in (("theta", theta), ("phi", phi)):
-        if not isinstance(x, torch.Tensor) or x.dim() != 2:
-            raise ValueError(f"{name}: expected a [rows, K] tensor")
-        if x.dtype != torch.float64:
-            raise ValueError(f"{name}: expected torch.float64, got {x.dtype}")
-        if not x.is_cuda:
-            raise ValueError(f"{name}: must be a GPU tensor")
-        if not x.is_contiguous():
-            raise ValueError(f"{name}: must be contiguous")
+    _table("theta", theta, "[rows, K]")
     dev = theta.device
-    if phi.device != dev:
-        raise ValueError(f"phi: on {phi.device}, expected {dev} (theta's device)")
+    _table("phi", phi, "[rows, K]", dev)
     (D, K), V = theta.shape, phi.shape[0]
     if K < 1 or phi.shape[1] != K:
         raise ValueError(f"theta / phi: row widths {K} and {phi.shape[1]} (one K >= 1)")
-    if not isinstance(doc, torch.Tensor) or doc.dim() != 1:
-        raise ValueError("doc: expected a 1-D tensor")
-    n = doc.numel()
-    if n >= 1 << 31:
-        raise ValueError(f"holdout_entries: {n} entries (n < 2^31)")
+    n = _vector("doc", doc, "holdout_entries")
     p_doc = _index("doc", doc, torch.int32, (n,), dev)
     p_word = _index("word", word, torch.int32, (n,), dev)
     p_t = _index("t", t, torch.int64, (n,), dev)
     p_seen = _index("word_seen", word_seen, torch.uint8, (V,), dev)
-    # index bounds (host check before a gather kernel touches memory)
-    if n:
-        for name, idx, lim in (("doc", doc, D), ("word", word, V)):
-            if int(idx.max()) >= lim or int(idx.min()) < 0:
-                raise ValueError(f"{name}: index out of range")
+    _in_range("doc", doc, 0, D)
+    _in_range("word", word, 0, V)
     ll = torch.empty(n, dtype=torch.float64, device=dev)
     if n == 0:
         return ll
@@ -1253,8 +1134,7 @@ def string_entropy(bytes_u8, offsets, max_blocks: int = 0):
     on every call.  ``max_blocks``: cap on the workgroups (tests: a small cap makes the grid-stride loop wrap).
     The kernel reads the ``entropy_table`` of the longest string of the call."""
     from .reference import entropy_table
-    if not isinstance(max_blocks, int) or max_blocks < 0:
-        raise ValueError(f"max_blocks must be a non-negative int, got {max_blocks!r}")
+    _max_blocks(max_blocks)
     if not isinstance(bytes_u8, torch.Tensor) or bytes_u8.dim() != 1:
         raise ValueError("bytes: expected a 1-D tensor")
     if not isinstance(offsets, torch.Tensor) or offsets.dim() != 1 or offsets.numel() < 1:

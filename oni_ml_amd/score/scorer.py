@@ -65,6 +65,24 @@ def build_model(tables, th, ph, default: float, device):
     return TopicModel.build(th, ph, default, device)
 
 
+def _ops(device):
+    """``(ops.hip, True)`` for a CUDA device, ``(ops.reference, False)`` otherwise: the one place that knows which
+    implementation a device gets.  The twins share names and signatures; imported at first use."""
+    if device.type == "cuda":
+        from ..ops import hip
+        return hip, True
+    from ..ops import reference
+    return reference, False
+
+
+def _i32(t):
+    return None if t is None else t.to(torch.int32).contiguous()
+
+
+def _i64(t):
+    return None if t is None else t.to(torch.int64).contiguous()
+
+
 def default_value(source: str, K: int, strict: bool) -> float:
     """Miss vector: flow 0.05 x 20, dns 0.1 x 20 in the reference (sums 1.0 and 2.0); 1/K when fixed."""
     if strict:
@@ -76,13 +94,8 @@ def score_votes(model, doc_a, word_a, doc_b=None, word_b=None, tol: float = floa
     """``score`` and, as a fifth value, the votes: for an EnsembleModel uint8 [n], the members whose own key is
     under ``tol``; None for one model."""
     if isinstance(model, EnsembleModel):
-        i32 = lambda t: None if t is None else t.to(torch.int32).contiguous()      # noqa: E731
-        if model.theta.device.type == "cuda":
-            from ..ops.hip import score_ensemble as fn
-        else:
-            from ..ops.reference import score_ensemble as fn
-        return fn(model.theta, model.phi, model.R, model.K, model.default, i32(doc_a), i32(word_a), i32(doc_b),
-                  i32(word_b), tol)
+        return _ops(model.theta.device)[0].score_ensemble(model.theta, model.phi, model.R, model.K, model.default,
+                                                          _i32(doc_a), _i32(word_a), _i32(doc_b), _i32(word_b), tol)
     return tuple(score(model, doc_a, word_a, doc_b, word_b, tol)) + (None,)
 
 
@@ -90,15 +103,11 @@ def score(model, doc_a, word_a, doc_b=None, word_b=None, tol: float = float("inf
     """Returns (score_a, score_b|None, key, flag) device tensors, for either model kind."""
     if isinstance(model, EnsembleModel):
         return tuple(score_votes(model, doc_a, word_a, doc_b, word_b, tol))[:4]
-    dev = model.theta.device
-    if dev.type == "cuda":
-        from ..ops import hip as H
-        return H.score_events(model.theta, model.phi, model.K, model.default, doc_a.to(torch.int32).contiguous(),
-                              word_a.to(torch.int32).contiguous(),
-                              None if doc_b is None else doc_b.to(torch.int32).contiguous(),
-                              None if word_b is None else word_b.to(torch.int32).contiguous(), tol)
-    from ..ops.reference import score as ref
-    return ref(model.theta, model.phi, model.K, model.default, doc_a, word_a, doc_b, word_b, tol)
+    O, gpu = _ops(model.theta.device)
+    if gpu:
+        return O.score_events(model.theta, model.phi, model.K, model.default, _i32(doc_a), _i32(word_a), _i32(doc_b),
+                              _i32(word_b), tol)
+    return O.score(model.theta, model.phi, model.K, model.default, doc_a, word_a, doc_b, word_b, tol)
 
 
 def key_quantiles(key: torch.Tensor, qs=(1e-4, 1e-3, 1e-2, 0.1, 0.5), sample: int = 1 << 18) -> dict:
@@ -137,13 +146,12 @@ def rank_flagged_counted(key: torch.Tensor, flag: torch.Tensor, limit: int):
     100,000, 100 M rows with N = 3,000: profiles/select_lowest.md), so there is no fall-back rule."""
     from ..ops import sortgroup as SG
     flag = flag.reshape(-1)
-    if key.device.type == "cuda":
-        from ..ops import hip as H
-        sel, flagged = H.select_lowest(key.reshape(-1).contiguous(), flag.to(torch.uint8).contiguous(), limit,
+    O, gpu = _ops(key.device)
+    if gpu:
+        sel, flagged = O.select_lowest(key.reshape(-1).contiguous(), flag.to(torch.uint8).contiguous(), limit,
                                        with_count=True)
     else:
-        from ..ops.reference import select_lowest
-        sel, flagged = select_lowest(key.reshape(-1), flag, limit, with_count=True)
+        sel, flagged = O.select_lowest(key.reshape(-1), flag, limit, with_count=True)
     if sel.numel() == 0:
         return np.zeros(0, np.int64), flagged
     order = SG.sort_stable(SG.gather(key, sel))[1]
@@ -154,25 +162,19 @@ def host_summary(doc_a, score_a, doc_b, score_b, num_docs: int, tol: float):
     """The scored sides folded per document, ``(events, flagged, min_score, worst, skipped)`` -- device tensors
     [num_docs] and an int (``ops.hip.host_summary`` on the GPU, ``ops.reference.host_summary`` elsewhere).
     ``doc_*``: the θ row of every side's IP or -1; ``worst``: side number 2 * event + side of the lowest score."""
-    i32 = lambda t: None if t is None else t.to(torch.int32).contiguous()      # noqa: E731
     f64 = lambda t: None if t is None else t.contiguous()                      # noqa: E731
-    if score_a.device.type == "cuda":
-        from ..ops import hip as H
-        return H.host_summary(i32(doc_a), f64(score_a), i32(doc_b), f64(score_b), int(num_docs), float(tol))
-    from ..ops.reference import host_summary as ref
-    return ref(i32(doc_a), f64(score_a), i32(doc_b), f64(score_b), int(num_docs), float(tol))
+    return _ops(score_a.device)[0].host_summary(_i32(doc_a), f64(score_a), _i32(doc_b), f64(score_b), int(num_docs),
+                                                float(tol))
 
 
 def group_rows_sum(table: torch.Tensor, order: torch.Tensor, seg_start: torch.Tensor, seg_end: torch.Tensor):
     """[G, W] sums of the rows ``table[order[seg_start[g] : seg_end[g]]]`` in the fixed block order of
     ``config.GROUP_BLOCK`` (``ops.hip.group_rows_sum`` on the GPU, ``ops.reference.group_rows_sum`` elsewhere:
     the same bits)."""
-    if table.device.type == "cuda":
-        from ..ops import hip as H
-        return H.group_rows_sum(table.contiguous(), order.to(torch.int32).contiguous(),
-                                seg_start.to(torch.int64).contiguous(), seg_end.to(torch.int64).contiguous())
-    from ..ops.reference import group_rows_sum as ref
-    return ref(table, order, seg_start, seg_end)
+    O, gpu = _ops(table.device)
+    if gpu:
+        return O.group_rows_sum(table.contiguous(), _i32(order), _i64(seg_start), _i64(seg_end))
+    return O.group_rows_sum(table, order, seg_start, seg_end)
 
 
 def model_tables3(model):
@@ -258,12 +260,8 @@ def explain_sides(model, gsum: torch.Tensor, doc: torch.Tensor, word: torch.Tens
     """``(cond [n, F], why uint8 [n])`` of the sides (``ops.hip.explain_sides`` on the GPU, its torch twin
     elsewhere); ``model``: a TopicModel or an EnsembleModel."""
     theta, phi = model_tables3(model)
-    i32 = lambda t: t.to(torch.int32).contiguous()      # noqa: E731
-    if theta.device.type == "cuda":
-        from ..ops.hip import explain_sides as fn
-    else:
-        from ..ops.reference import explain_sides as fn
-    return fn(theta.contiguous(), phi.contiguous(), gsum.contiguous(), i32(doc), i32(word), i32(grow), model.default)
+    return _ops(theta.device)[0].explain_sides(theta.contiguous(), phi.contiguous(), gsum.contiguous(), _i32(doc),
+                                               _i32(word), _i32(grow), model.default)
 
 
 def expect_sides(model, seg: FieldSegments, doc: torch.Tensor, word: torch.Tensor, grow: torch.Tensor):
@@ -273,15 +271,10 @@ def expect_sides(model, seg: FieldSegments, doc: torch.Tensor, word: torch.Tenso
     word itself.  ``path``: ``"blocks"`` (``ops.hip.expect_sides``) on the GPU, ``"cpu"`` (its torch twin: the same
     bits) elsewhere; ``model``: a TopicModel or an EnsembleModel."""
     theta, phi = model_tables3(model)
-    i32 = lambda t: t.to(torch.int32).contiguous()      # noqa: E731
-    i64 = lambda t: t.to(torch.int64).contiguous()      # noqa: E731
-    args = (theta.contiguous(), phi.contiguous(), i32(seg.order), i64(seg.seg_start), i64(seg.seg_end), i32(doc),
-            i32(word), i32(grow), model.default)
-    if theta.device.type == "cuda":
-        from ..ops import hip as H
-        return H.expect_sides(*args), H.EXPECT_FORMS[0]
-    from ..ops.reference import expect_sides as ref
-    return ref(*args), "cpu"
+    O, gpu = _ops(theta.device)
+    out = O.expect_sides(theta.contiguous(), phi.contiguous(), _i32(seg.order), _i64(seg.seg_start), _i64(seg.seg_end),
+                         _i32(doc), _i32(word), _i32(grow), model.default)
+    return out, O.EXPECT_FORMS[0] if gpu else "cpu"
 
 
 def expect_form() -> str:
@@ -297,12 +290,7 @@ def tail_mass(model, doc: torch.Tensor, word: torch.Tensor):
     ``model``: a TopicModel (one member through a ``[rows, 1, K]`` view) or an EnsembleModel; ``doc`` / ``word``: θ /
     φ rows or -1."""
     theta, phi = model_tables3(model)
-    i32 = lambda t: t.to(torch.int32).contiguous()      # noqa: E731
-    if theta.device.type == "cuda":
-        from ..ops.hip import tail_mass as fn
-    else:
-        from ..ops.reference import tail_mass as fn
-    return fn(theta.contiguous(), phi.contiguous(), i32(doc), i32(word))
+    return _ops(theta.device)[0].tail_mass(theta.contiguous(), phi.contiguous(), _i32(doc), _i32(word))
 
 
 def tail_pairs(model, doc: torch.Tensor, word: torch.Tensor):
@@ -317,7 +305,7 @@ def tail_pairs(model, doc: torch.Tensor, word: torch.Tensor):
     from ..ops import sortgroup as SG
     theta, phi = model_tables3(model)
     theta, phi = theta.contiguous(), phi.contiguous()
-    d32, w32 = doc.to(torch.int32).contiguous(), word.to(torch.int32).contiguous()
+    d32, w32 = _i32(doc), _i32(word)
     if theta.device.type != "cuda":
         from ..ops.reference import tail_mass as ref
         return ref(theta, phi, d32, w32), "cpu"
@@ -336,12 +324,9 @@ def peer_topn(model, query: torch.Tensor, n: int):
     row left out (``ops.hip.peer_topn`` on the GPU, its torch twin elsewhere: the same bits).  ``path``: the
     kernel's form (``ops.hip.peer_theta_path``) or ``"cpu"``; ``model``: a TopicModel or an EnsembleModel."""
     theta = model_tables3(model)[0].contiguous()
-    q32 = query.to(torch.int32).contiguous()
-    if theta.device.type == "cuda":
-        from ..ops import hip as H
-        return H.peer_topn(theta, q32, n), H.peer_theta_path(int(theta.shape[1]), int(theta.shape[2]))
-    from ..ops.reference import peer_topn as ref
-    return ref(theta, q32, n), "cpu"
+    O, gpu = _ops(theta.device)
+    out = O.peer_topn(theta, _i32(query), n)
+    return out, O.peer_theta_path(int(theta.shape[1]), int(theta.shape[2])) if gpu else "cpu"
 
 
 def peer_scores(model, rows: torch.Tensor, count: torch.Tensor, doc: torch.Tensor, word: torch.Tensor) -> torch.Tensor:
@@ -368,11 +353,8 @@ def column_topn(table: torch.Tensor, n: int):
     the GPU, its torch twin elsewhere: the same bits).  ``path``: the kernel's form (``ops.hip.topic_path``) or
     ``"cpu"``."""
     table = table.contiguous()
-    if table.device.type == "cuda":
-        from ..ops import hip as H
-        return H.column_topn(table, n), H.topic_path(n, int(table.shape[1]))
-    from ..ops.reference import column_topn as ref
-    return ref(table, n), "cpu"
+    O, gpu = _ops(table.device)
+    return O.column_topn(table, n), O.topic_path(n, int(table.shape[1])) if gpu else "cpu"
 
 
 def row_dominant(table3: torch.Tensor):
@@ -380,11 +362,8 @@ def row_dominant(table3: torch.Tensor):
     (row, member) of ``table3`` [rows, R, K] and the rows per (member, topic) (``ops.hip.row_dominant`` on the GPU,
     its torch twin elsewhere).  ``path``: ``"lanes"`` or ``"cpu"``."""
     table3 = table3.contiguous()
-    if table3.device.type == "cuda":
-        from ..ops.hip import row_dominant as fn
-        return fn(table3), "lanes"
-    from ..ops.reference import row_dominant as ref
-    return ref(table3), "cpu"
+    O, gpu = _ops(table3.device)
+    return O.row_dominant(table3), "lanes" if gpu else "cpu"
 
 
 def topic_sides(model, doc: torch.Tensor, word: torch.Tensor):
@@ -394,12 +373,8 @@ def topic_sides(model, doc: torch.Tensor, word: torch.Tensor):
     elsewhere: the same bits).  ``model``: a TopicModel or an EnsembleModel; ``doc`` / ``word``: θ / φ rows or -1;
     ``path``: ``"lanes"`` or ``"cpu"``."""
     theta, phi = model_tables3(model)
-    i32 = lambda t: t.to(torch.int32).contiguous()      # noqa: E731
-    if theta.device.type == "cuda":
-        from ..ops.hip import topic_sides as fn
-        return fn(theta.contiguous(), phi.contiguous(), i32(doc), i32(word)), "lanes"
-    from ..ops.reference import topic_sides as ref
-    return ref(theta.contiguous(), phi.contiguous(), i32(doc), i32(word)), "cpu"
+    O, gpu = _ops(theta.device)
+    return O.topic_sides(theta.contiguous(), phi.contiguous(), _i32(doc), _i32(word)), "lanes" if gpu else "cpu"
 
 
 def column_l1(A: torch.Tensor, B: torch.Tensor, ia: Optional[torch.Tensor] = None,
@@ -408,12 +383,8 @@ def column_l1(A: torch.Tensor, B: torch.Tensor, ia: Optional[torch.Tensor] = Non
     blocks of ``config.MATCH_BLOCK`` pairs (``ops.hip.column_l1`` on the GPU, its torch twin elsewhere: the same
     bits).  ``ia`` / ``ib``: int64 rows, both None for the identity.  ``path``: ``"hip"`` or ``"cpu"``."""
     A, B = A.contiguous(), B.contiguous()
-    i64 = lambda t: None if t is None else t.to(torch.int64).contiguous()      # noqa: E731
-    if A.device.type == "cuda":
-        from ..ops.hip import column_l1 as fn
-        return fn(A, B, i64(ia), i64(ib)), "hip"
-    from ..ops.reference import column_l1 as ref
-    return ref(A, B, i64(ia), i64(ib)), "cpu"
+    O, gpu = _ops(A.device)
+    return O.column_l1(A, B, _i64(ia), _i64(ib)), "hip" if gpu else "cpu"
 
 
 def rank_hosts(min_score: torch.Tensor, flagged: torch.Tensor, limit: Optional[int] = None) -> np.ndarray:
